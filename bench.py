@@ -5,8 +5,16 @@ A "step" is ONE ENCODED FRAME of a synthetic 1920x1080 8-bit 4:2:0 clip through 
 x265amd_encoder_open / encode / close, the reference's x265_encoder_* entry points, source/x265.h:2412-2471): mode decision of every CTU
 (Analysis::compressCTU with the --preset medium analysis settings: rd 3, hex / subme 2, 3 references, early skip, rskip, psy-rd 2, sign hiding,
 4 B frames), in-loop deblocking + SAO, CABAC, slice NAL units -- the whole byte stream, which must equal the reference ENCODER's (oracle/_ref/x265_ref8,
-the reference compiled from /root/reference; same clip, same options) byte for byte.  That comparison is made in the run and reported; the
+the reference built by oracle/build_ref.sh; same clip, same options) byte for byte.  That comparison is made in a --full run and reported; the
 reference's own wall time on the host cores of the same box is the CPU baseline (kind "reference").
+
+A plain run does only what the headline needs: set-up, the warm-up, the K timed frames, the outputs (--dump-outputs DIR) and the JSON line.  --full adds
+everything else the line reports: the reference encoder's CPU baseline and stream comparison, the host-input encode, the 60- and 240-frame clips, the
+3840x2160 / Main 10 / 7680x4320 configurations and the kernel workload (the --no-* options leave parts of it out).
+
+--dump-outputs DIR: after the timed encode, what it returned -- DIR/stream.npy, the whole byte stream (headers and every coded picture's NAL units), and
+DIR/last_picture.npy, the NAL units the last step handed out -- one byte value per float32 element; a stream larger than the budget is written as a fixed,
+seeded sample of its bytes, with their positions in DIR/stream_index.npy.  The clip depends on the arguments alone, so two builds can be compared byte for byte.
 
 Timed region: W warm-up frames are encoded (untimed, their own encoder object), then EXACTLY K frames between barriers: from the first
 x265amd_encoder_encode of the K-frame clip to the last flushed NAL unit.  The boundary takes host pictures (as x265_picture does): each input frame
@@ -20,11 +28,11 @@ Multi-GPU (one process per GPU, torch.distributed nccl == RCCL), two ways (DESIG
 The GOP structure is the lookahead's (--b-adapt 2, B pyramid, open GOPs, scene-cut detection: the preset as it comes), not fixed mini-GOPs.
 
 The kernels of the hot path are timed on their own in bench_kernels.py (a frame's worth of motion searches, intra scans, transform chains, merge
-costs, coefficient codings and filters as batches): its figures ride along as `kernel_workload`.  The `roofline` object prices the kernel the timed
+costs, coefficient codings and filters as batches): its figures ride along as `kernel_workload` in a --full run.  The `roofline` object prices the kernel the timed
 region actually runs: k_job_server, resident for the whole encode -- the algorithmic bytes of every command it ran (counted on the device) over its launch
 duration (HIP events on its stream), and the share of its resident time spent inside command bodies (`busy_frac`).
 
-Contract: python bench.py --gpus N --steps K --warmup W ; prints ONE JSON line on rank 0.
+Contract: python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR] ; prints ONE JSON line on rank 0.
 """
 import argparse
 import ctypes as C
@@ -299,6 +307,25 @@ def reference_encode(frames, cli=None, depth=8, runs=("default", "f1")):
         os.rmdir(d)
 
 
+DUMP_BYTES = 64 << 20                # --dump-outputs: at most this many bytes of .npy data in all
+
+
+def dump_outputs(out_dir, stream, marks):
+    """what the timed encode returned, as float32 byte values: the whole stream and the last step's NAL units (the last coded picture);
+    a stream beyond the budget is written as a fixed sample (seed 0) of its bytes, in stream order, with their positions"""
+    os.makedirs(out_dir, exist_ok=True)
+    data = np.frombuffer(stream, dtype=np.uint8)
+    last = data[marks[-1]:] if marks else data[:0]
+    room = (DUMP_BYTES - 4 * len(last)) // 4 - 1024      # elements left for the stream (and the index beside a sample, 8 bytes each)
+    if len(data) <= room:
+        np.save(os.path.join(out_dir, "stream.npy"), data.astype(np.float32))
+    else:
+        idx = np.sort(np.random.default_rng(0).choice(len(data), size=room // 3, replace=False))
+        np.save(os.path.join(out_dir, "stream.npy"), data[idx].astype(np.float32))
+        np.save(os.path.join(out_dir, "stream_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, "last_picture.npy"), last.astype(np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -316,6 +343,9 @@ def main():
     ap.add_argument("--no-extra-configs", action="store_true", help="skip the 3840x2160 --preset slow and Main 10 encodes that the 1080p single-GPU run reports beside the bench line")
     ap.add_argument("--no-8k", action="store_true", help="skip the three 7680x4320 --preset veryslow --rd 6 frames (BASELINE configs[4]) among the extra configurations: they add about two minutes")
     ap.add_argument("--no-scene-clip", action="store_true", help="skip the 60-frame clip with both re-seeds inside that the 1080p single-GPU run reports beside the bench line (`scene_change_clip`)")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: the reference encoder's CPU baseline and stream comparison, the host-input "
+                    "encode, the 60- and 240-frame clips, the extra sizes and configurations and the kernel workload (the --no-* options above leave parts out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed encode, write what it returned as DIR/stream.npy and DIR/last_picture.npy (float32 byte values)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -393,10 +423,12 @@ def main():
                 json.dump(encode.last_marks, f_)
     else:
         sizes = [(len(stream), hashlib.md5(stream).hexdigest())]
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, stream, encode.last_marks)
 
     line = None
     if rank == 0:
-        ref = None if (world > 1 or args.no_cpu_baseline) else reference_encode(frames, runs=("default", "f1", "pools16"))
+        ref = None if (world > 1 or args.no_cpu_baseline or not args.full) else reference_encode(frames, runs=("default", "f1", "pools16"))
         if ref is not None:
             same = ref["default"]["stream"] == stream
             cpu = {"value": K / ref["default"]["seconds"], "unit": "frames/s", "cores": ref["cores"], "kind": "reference",
@@ -442,7 +474,7 @@ def main():
                                     "by the latency of the reference's serial decision chain, not by bandwidth"},
         }
     # ---- the same encode with the frames handed over as HOST buffers (the reference API's form): padded on the host and sent over the bus inside the timed region ----
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         try:
             stream_h, dt_h = encode(T, L, frames, 0, 0, sync, host_input=True)
             line["host_input"] = {"value": K / dt_h, "unit": "frames/s", "stream_equals": bool(stream_h == stream),
@@ -450,7 +482,7 @@ def main():
         except Exception as exc:         # noqa: BLE001
             line["host_input"] = {"error": repr(exc)}
     # ---- SURVEY.md section 8d's whole clip: 60 frames with both re-seeds of the noise field inside (pictures with new content everywhere) ----
-    if rank == 0 and world == 1 and args.res == "1080p" and not args.no_scene_clip and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and args.res == "1080p" and not args.no_scene_clip and not args.no_cpu_baseline:
         try:
             frames60 = bench_clip(0, 60)
             stream60, dt60 = encode(T, L, frames60, 0, 0, sync)
@@ -479,7 +511,7 @@ def main():
         except Exception as exc:
             line["long_clip"] = {"error": repr(exc)}
     # ---- the same encode at 3840x2160 (BASELINE.json's metric names both sizes; the bench line is the 1080p one): reported beside it, never instead of it ----
-    if rank == 0 and world == 1 and args.res == "1080p" and not args.no_2160p and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and args.res == "1080p" and not args.no_2160p and not args.no_cpu_baseline:
         try:
             W, H = 3840, 2160
             frames4 = bench_clip(0, K)
@@ -497,7 +529,7 @@ def main():
         finally:
             W, H = 1920, 1080
     # ---- BASELINE.json configs[2] and configs[3] at their stated size: 3840x2160 --preset slow (8-bit) and 3840x2160 Main 10 --preset medium, stream compared in the run ----
-    if rank == 0 and world == 1 and args.res == "1080p" and not args.no_extra_configs and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and args.res == "1080p" and not args.no_extra_configs and not args.no_cpu_baseline:
         # (configs[4], 7680x4320 10-bit --preset veryslow --rd 6, rides along since round 5's end with three frames -- I, P and a B picture: it goes CU by CU through the host's path,
         #  what the line says is where that stands against the reference, not a figure anybody has worked on)
         extra = (("also_2160p_slow", 8, 3, T.SLOW_TOOLS, ["--preset", "slow"], (3840, 2160), 12, 2, 2),
@@ -528,7 +560,7 @@ def main():
             finally:
                 W, H = 1920, 1080
     # ---- the hot-path kernels on their own (bench_kernels.py): a frame's worth of batched block operations ----
-    if not args.no_kernel_workload:
+    if args.full and not args.no_kernel_workload:
         import bench_kernels
         kargs = bench_kernels.parse_args(["--gpus", str(args.gpus), "--steps", str(max(5, min(20, K))), "--warmup", "3", "--res", args.res] + (["--no-cpu-baseline"] if args.no_cpu_baseline else []))
         kw = bench_kernels.run(kargs)

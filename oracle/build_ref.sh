@@ -17,6 +17,7 @@
 #   oracle/_ref/x265_dropinD      reference encoder + optional x265amd_setup_primitives() override (oracle/ref_encode_with_table.cpp)
 #   oracle/_ref/x265_rc_dumpD     the reference encoder + a per-picture record of its rate control's and lookahead's decisions (oracle/ref_rc_dump.cpp)
 #   oracle/_ref/x265_abi_driverD  a libx265 client over another library's x265_api table (oracle/abi_driver.cpp; tests/test_x265_api_abi.py)
+#   oracle/_ref/include/          the reference's headers (source/**/*.h), for the layout tests
 set -euo pipefail
 REF=${X265_REFERENCE:-/root/reference}
 HERE=$(cd "$(dirname "$0")" && pwd)
@@ -30,6 +31,10 @@ SRC=$REF/source
 BUILD=$(sed -n 's/^set(X265_BUILD \([0-9]*\)).*/\1/p' "$SRC/CMakeLists.txt")
 mkdir -p "$OUT/cfg"
 sed "s/\${X265_BUILD}/$BUILD/" "$SRC/x265_config.h.in" > "$OUT/cfg/x265_config.h"
+# the reference's headers as they lie under source/, for the tests that check our layouts against them (tests/test_primitive_table_layout.py,
+# tests/test_x265_api_abi.py): those compile against oracle/_ref alone
+rm -rf "$OUT/include" && mkdir -p "$OUT/include"
+(cd "$SRC" && find . -name '*.h' -exec cp --parents {} "$OUT/include/" \;)
 VER="3.6+1-aa7f602f7"
 
 LIBSRC=$(ls "$SRC"/common/*.cpp "$SRC"/encoder/*.cpp | grep -v winxp.cpp)

@@ -10,8 +10,8 @@ ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-timeout 900 python3 $ROOT/bench.py "$@" > "$OUT/bench.json" 2> "$OUT/bench.err"
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/kt" -- python3 $ROOT/bench.py --steps 20 --warmup 5 --no-cpu-baseline "$@" > "$OUT/kt.log" 2>&1
+timeout 900 python3 $ROOT/bench.py --full "$@" > "$OUT/bench.json" 2> "$OUT/bench.err"
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/kt" -- python3 $ROOT/bench.py --steps 20 --warmup 5 --full --no-cpu-baseline "$@" > "$OUT/kt.log" 2>&1
 timeout 600 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/fetch" -- python3 $ROOT/bench_kernels.py --steps 5 --warmup 1 --no-cpu-baseline > "$OUT/fetch.log" 2>&1
 timeout 600 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$OUT/write" -- python3 $ROOT/bench_kernels.py --steps 5 --warmup 1 --no-cpu-baseline > "$OUT/write.log" 2>&1
 python3 $ROOT/profiles/reduce.py "$OUT" "$TAG" "$ROUND"

@@ -1,6 +1,6 @@
 """The slot map the product uses to fill an EncoderPrimitives-shaped table (x265-amod_amd/host/primitive_table.h)
 is checked against the reference's own header with offsetof static_asserts (tests/layout_check.cpp).  Needs
-/root/reference and oracle/_ref/cfg (this container only)."""
+oracle/_ref/cfg and oracle/_ref/include (oracle/build_ref.sh: where the reference's sources are present)."""
 import os
 import subprocess
 
@@ -8,10 +8,10 @@ import pytest
 
 import hevc_testlib as T
 
-REF_SRC = "/root/reference/source"
+REF_SRC = os.path.join(T.REF_DIR, "include")      # the reference's source/ headers (oracle/build_ref.sh)
 
 
-@pytest.mark.skipif(not (os.path.isdir(REF_SRC) and os.path.isdir(os.path.join(T.REF_DIR, "cfg"))), reason="needs /root/reference + oracle/_ref")
+@pytest.mark.skipif(not (os.path.isdir(REF_SRC) and os.path.isdir(os.path.join(T.REF_DIR, "cfg"))), reason="needs oracle/_ref with the reference's headers (oracle/build_ref.sh)")
 @pytest.mark.parametrize("depth", [8, 10])
 def test_layout(depth, tmp_path):
     cmd = ["g++", "-std=gnu++17", "-fsyntax-only", "-w", "-Wno-invalid-offsetof",

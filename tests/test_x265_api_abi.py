@@ -226,16 +226,17 @@ def test_param_default_preset_opens_and_encodes(preset):
 
 
 @pytest.mark.needs_ref
-def test_generated_layout_matches_reference_header():
-    if not os.path.isdir("/root/reference/source"):
-        pytest.skip("the reference's header is only present in the build container")
-    cmd = ["g++", "-std=gnu++11", "-fsyntax-only", "-I" + os.path.join(T.REF_DIR, "cfg"), "-I/root/reference/source", "-I" + os.path.join(T.PKG_DIR, "host"),
+def test_generated_layout_matches_reference_header(tmp_path):
+    ref_src = os.path.join(T.REF_DIR, "include")        # the reference's source/ headers (oracle/build_ref.sh)
+    if not os.path.isdir(ref_src):
+        pytest.skip("oracle/_ref/include (the reference's headers) is not built")
+    cmd = ["g++", "-std=gnu++11", "-fsyntax-only", "-I" + os.path.join(T.REF_DIR, "cfg"), "-I" + ref_src, "-I" + os.path.join(T.PKG_DIR, "host"),
            os.path.join(T.ROOT, "tests", "abi_layout_check.cpp")]
     r = subprocess.run(cmd, capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-3000:]
     # and the committed header is what the generator prints today
-    exe = "/tmp/x265amd_gen_abi"
-    r = subprocess.run(["g++", "-std=gnu++11", "-I" + os.path.join(T.REF_DIR, "cfg"), "-I/root/reference/source", os.path.join(T.ROOT, "oracle", "gen_abi_layout.cpp"), "-o", exe],
+    exe = str(tmp_path / "gen_abi")
+    r = subprocess.run(["g++", "-std=gnu++11", "-I" + os.path.join(T.REF_DIR, "cfg"), "-I" + ref_src, os.path.join(T.ROOT, "oracle", "gen_abi_layout.cpp"), "-o", exe],
                        capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-3000:]
     assert subprocess.run([exe], capture_output=True, text=True).stdout == open(os.path.join(T.PKG_DIR, "host", "x265_abi_layout.h")).read()

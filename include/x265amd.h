@@ -558,6 +558,10 @@ int x265amd_extend_border_rows(void* stream, x265amd_pixel* d_pic, intptr_t stri
  * with line 0 the top margin above them (their corners under the same conditions). */
 int x265amd_extend_border_band(void* stream, x265amd_pixel* d_pic, intptr_t stride, int width, int height, int marginX, int marginY, int y_begin, int y_end,
                                int x_begin, int x_end, int left, int right);
+/* the same for the three planes of a 4:2:0 picture in one launch: luma geometry given (all even), the chroma planes take half of everything.  What the filter thread
+ * of a picture calls behind every column chunk it finishes. */
+int x265amd_extend_border_band_420(void* stream, x265amd_pixel* d_y, x265amd_pixel* d_u, x265amd_pixel* d_v, intptr_t stride, intptr_t cstride, int width, int height,
+                                   int marginX, int marginY, int y_begin, int y_end, int x_begin, int x_end, int left, int right);
 int x265amd_weight_plane(void* stream, const x265amd_pixel* d_src, x265amd_pixel* d_dst, intptr_t stride, int width, int height,
                          int marginX, int marginY, int inputWeight, int inputOffset, int log2WeightDenom);
 
@@ -640,6 +644,28 @@ int x265amd_sao_stats_rows_cols(void* stream, const uint64_t rec_planes[3], cons
                                 int width, int height, int32_t* d_count, int32_t* d_offset_org, int ctu_row_begin, int ctu_row_end, int ctu_col_begin, int ctu_col_end);
 int x265amd_sao_apply_rows_cols(void* stream, const uint64_t src_planes[3], const uint64_t dst_planes[3], intptr_t stride, intptr_t cstride,
                                 int width, int height, const x265amd_sao_ctu* d_params, int ctu_row_begin, int ctu_row_end, int x_begin, int x_end);
+
+/* --- the column forms' schedule (host code, host/filter_plan.cpp): which column chunks of which CTU rows the filter thread of a picture takes next while the
+ * picture's analysis still advances, and which samples are final behind them.  A chunk [col_begin, col_end) of CTU row `row` is taken in two steps.
+ * TOP: x265amd_deblock_units_rect of unit rows y4_begin .. rec_y4_end - 1, unit columns rec_x4_begin .. rec_x4_end - 1, then x265amd_deblock_rows_cols of unit rows
+ * y4_begin .. y4_end - 1 (the row's first eight lines and its top horizontal edge).  FULL: x265amd_deblock_rows_cols of unit rows y4_begin .. y4_end - 1 (nothing when
+ * they are equal), x265amd_sao_stats_rows_cols and, behind a synchronisation, x265amd_sao_rdo_cols of the chunk.  A finish range is what the steps of a sweep make
+ * final: x265amd_sao_apply_rows_cols and x265amd_extend_border_band_420 of the sample columns x_begin .. x_end - 1 of CTU row `row` (lines y_begin .. y_end - 1;
+ * left margin when x_begin == 0, right margin when x_end == width), published to the pictures that reference this one behind a second synchronisation. */
+enum { X265AMD_FILTER_TOP = 0, X265AMD_FILTER_FULL = 1 };
+typedef struct x265amd_filter_step { int32_t kind, row, col_begin, col_end, y4_begin, y4_end, rec_y4_end, rec_x4_begin, rec_x4_end; } x265amd_filter_step;
+typedef struct x265amd_filter_finish { int32_t row, x_begin, x_end, y_begin, y_end; } x265amd_filter_finish;
+/* One sweep.  analysed[r]: CTUs of row r analysed (a snapshot; the rows only advance).  done_top / done_full[r]: CTU columns of row r whose TOP / FULL step has
+ * been taken, pub_x[r]: sample columns of row r that are final; all zero before the first sweep, updated in place.  min_chunk / min_chunk_last: the fewest CTUs of
+ * a chunk that does not end its row, in ordinary rows / in the last three CTU rows.  early_top: TOP does not wait for the row below.  steps (room for two per CTU
+ * row) come in the order they must be enqueued, finish ranges (room for one per CTU row) likewise.  Everything is done when done_full[r] is the number of CTU
+ * columns in every row. */
+int x265amd_filter_plan(int width, int height, const int32_t* analysed, int32_t* done_top, int32_t* done_full, int32_t* pub_x,
+                        int min_chunk, int min_chunk_last, int early_top,
+                        x265amd_filter_step* steps, int* num_steps, x265amd_filter_finish* finish, int* num_finish);
+/* 1 when x265amd_filter_plan would return a step for this snapshot or everything is done, 0 when the filter thread has to wait for the analysis */
+int x265amd_filter_ready(int width, int height, const int32_t* analysed, const int32_t* done_top, const int32_t* done_full,
+                         int min_chunk, int min_chunk_last, int early_top);
 
 /* --- final entropy coding of CTUs: the CABAC write pass, host code.  Entropy::encodeCTU / encodeCU /
  * encodeTransform / codePredInfo / codeCoeffNxN and the arithmetic coder (reference: source/encoder/entropy.cpp:768-1222, :1431-2200,

@@ -4244,3 +4244,132 @@ RC_CASES = {
     "rc_tune_zerolatency/": ((416, 240), 26, 8, 2, dict(PRESET_BASE, bFrameAdaptive=0, bframes=0, lookaheadDepth=0, scenecutThreshold=0, cuTree=0, frameNumThreads=1),
                              ["--preset", "medium", "--tune", "zerolatency"]),
 }
+
+
+# ---- the in-loop filters by columns: schedules for x265amd_filter_plan (host/filter_plan.cpp) and one combined picture per geometry ----
+FILTER_STEP_DT = np.dtype([(n, "<i4") for n in ("kind", "row", "col_begin", "col_end", "y4_begin", "y4_end", "rec_y4_end", "rec_x4_begin", "rec_x4_end")])
+FILTER_FINISH_DT = np.dtype([(n, "<i4") for n in ("row", "x_begin", "x_end", "y_begin", "y_end")])
+FILTER_TOP, FILTER_FULL = 0, 1
+FILTER_SCHEDULES = ("wavefront", "raster", "all", "single")
+FILTER_MARGIN = (96, 80)            # the encoder's luma margins (chroma: half)
+SAO_CARRY_BYTES = 160 + 8           # X265AMD_CTX_STRIDE + 8 (include/x265amd.h: x265amd_sao_rdo_cols)
+
+
+def filter_schedule(kind, seed, ctuW, ctuH, max_step=None):
+    """a seeded sequence of snapshots of a picture's analysis (analysedCols[r] per CTU row, monotone, the last one complete):
+    wavefront -- row r is never ahead of analysedCols[r - 1] - 1 unless the row above is complete, random increments of up to max_step CTUs (2 * ctuW unless
+                 given) per snapshot (what the encoder's rows do);
+    raster    -- a row completes before the next begins, random increments;
+    all       -- everything analysed before the filter first looks;
+    single    -- one CTU per snapshot, in wavefront order."""
+    rng = np.random.default_rng(seed)
+    a = [0] * ctuH
+    out = []
+
+    def eligible():
+        return [r for r in range(ctuH) if a[r] < ctuW and (r == 0 or a[r - 1] == ctuW or a[r] + 1 <= a[r - 1] - 1)]
+
+    if kind == "all":
+        return [[ctuW] * ctuH]
+    if kind == "raster":
+        for r in range(ctuH):
+            while a[r] < ctuW:
+                a[r] = min(ctuW, a[r] + int(rng.integers(1, ctuW + 1)))
+                out.append(list(a))
+        return out
+    if kind == "single":
+        while any(v < ctuW for v in a):
+            for r in eligible():            # one pass down the wavefront, a snapshot per CTU
+                a[r] += 1
+                out.append(list(a))
+        return out
+    assert kind == "wavefront", kind
+    while any(v < ctuW for v in a):
+        for _ in range(int(rng.integers(1, (max_step or 2 * ctuW) + 1))):
+            el = eligible()
+            if not el:
+                break
+            a[el[int(rng.integers(0, len(el)))]] += 1
+        out.append(list(a))
+    return out
+
+
+def filter_min_chunks(m, ctuW):
+    """(min_chunk, min_chunk_last) of filterRowsCols for the three values a chunk minimum can take: 1 (X265AMD_FILTER_CHUNK=1), 2 (P pictures: 1 in the last three
+    rows), 'w' (B pictures: whole rows)"""
+    return {1: (1, 1), 2: (2, 1), "w": (ctuW, ctuW)}[m]
+
+
+def filter_sweeps(L, width, height, schedule, min_chunk, min_chunk_last, early_top):
+    """the sweeps the filter thread of a picture takes for a sequence of snapshots: x265amd_filter_plan after every snapshot for as long as it returns steps
+    (x265amd_filter_ready must say the same).  Each sweep: dict(steps, finish, pub_x (after the sweep), analysed)."""
+    ctuW, ctuH = (width + 63) // 64, (height + 63) // 64
+    done_top, done_full, pub_x = (np.zeros(ctuH, np.int32) for _ in range(3))
+    steps = np.zeros(2 * ctuH, FILTER_STEP_DT); finish = np.zeros(ctuH, FILTER_FINISH_DT)
+    ns, nf = C.c_int(0), C.c_int(0)
+    out = []
+    for snap in schedule:
+        an = np.array(snap, np.int32)
+        while True:
+            all_done = bool((done_full == ctuW).all())
+            ready = L.lib.x265amd_filter_ready(width, height, _ptr(an), _ptr(done_top), _ptr(done_full), min_chunk, min_chunk_last, early_top)
+            rc = L.lib.x265amd_filter_plan(width, height, _ptr(an), _ptr(done_top), _ptr(done_full), _ptr(pub_x), min_chunk, min_chunk_last, early_top,
+                                           _ptr(steps), C.byref(ns), _ptr(finish), C.byref(nf))
+            assert rc == 0, rc
+            assert ready == int(ns.value > 0 or all_done), (ready, ns.value, all_done, snap)
+            if ns.value == 0:
+                assert nf.value == 0
+                break
+            out.append(dict(steps=steps[:ns.value].copy(), finish=finish[:nf.value].copy(), pub_x=pub_x.copy(), analysed=list(snap)))
+    assert (done_top == ctuW).all() and (done_full == ctuW).all() and (pub_x == width).all(), (done_top, done_full, pub_x)
+    return out
+
+
+def filter_case(depth, seed, width, height, slice_b=True, bypass=False):
+    """one picture for the column forms of the in-loop filters: deblock_case's coding tree, records and blocky planes re-laid into planes with the encoder's margins
+    (the margins poisoned with a valid sample value: nothing may read them), a source picture derived from the unfiltered picture (as sao_case derives fenc from
+    rec) so that the SAO decision really switches offsets on, and cabac_case's si / units for the decision."""
+    c = deblock_case(depth, seed, width, height, slice_b=slice_b, bypass=bypass)
+    rng = np.random.default_rng(seed + 7777)
+    pmax = (1 << depth) - 1
+    dt = c["planes"][0].dtype
+    poison = 0xA5 if depth == 8 else 0x2A5
+    mx, my = FILTER_MARGIN
+    stride, cstride = width + 2 * mx, width // 2 + mx
+    rec, fenc = [], []
+    for k, (w, h, st, ax, ay, om) in enumerate(((width, height, stride, mx, my, 16), (width // 2, height // 2, cstride, mx // 2, my // 2, 8), (width // 2, height // 2, cstride, mx // 2, my // 2, 8))):
+        pic = c["planes"][k][om:om + h, om:om + w].astype(np.int64)
+        full = np.full((h + 2 * ay, st), poison, dt)
+        full[ay:ay + h, ax:ax + w] = pic
+        src = np.zeros((h + 2 * ay, st), dt)
+        # the source: the unfiltered picture pulled halfway towards its local mean (local extremes are what the edge offsets correct) plus small noise
+        e = np.pad(pic, 1, mode="edge")
+        mean = (e[:-2, 1:-1] + e[2:, 1:-1] + e[1:-1, :-2] + e[1:-1, 2:] + 2) >> 2
+        src[ay:ay + h, ax:ax + w] = np.clip(pic + ((mean - pic) >> 1) + rng.integers(-2, 3, pic.shape) * (1 << (depth - 8)), 0, pmax)
+        rec.append(full); fenc.append(src)
+    cab = cabac_case(seed, width, height, 0 if slice_b else 1)
+    return dict(c, rec=rec, fenc=fenc, stride=stride, cstride=cstride, org=(my * stride + mx, (my // 2) * cstride + mx // 2), margin=(mx, my), poison=poison,
+                si=np.array([cab["si"]], SLICE_INFO_DT), cu_units=np.ascontiguousarray(cab["units"].reshape(-1)), referenced=int(not slice_b),
+                ctuW=(width + 63) // 64, ctuH=(height + 63) // 64, nctu=((width + 63) // 64) * ((height + 63) // 64))
+
+
+def filter_case_expected(O, P, c):
+    """the picture through the picture-wide forms on the CPU: the oracle's deblocking, statistics, offsets and borders; the product's host decision (x265amd_sao_rdo with
+    two frame threads) in between.  Returns dict(D, count, org, params, F)."""
+    w, h = c["width"], c["height"]
+    D = [p.copy() for p in c["rec"]]
+    O.lib.orc_deblock_picture(_ptr(_plane_ptrs(D, c["org"])), C.c_int64(c["stride"]), C.c_int64(c["cstride"]), w, h, _ptr(c["units"]),
+                              c["beta"], c["tc"], c["cb"], c["cr"], c["bypass"], 3)
+    n = c["nctu"] * 3 * 5 * 32
+    cnt = np.zeros(n, np.int32); org = np.zeros(n, np.int32)
+    O.lib.orc_sao_stats_picture(_ptr(_plane_ptrs(D, c["org"])), _ptr(_plane_ptrs(c["fenc"], c["org"])), C.c_int64(c["stride"]), C.c_int64(c["cstride"]), w, h, _ptr(cnt), _ptr(org))
+    params = np.zeros(c["nctu"], SAO_CTU_DT); flags = np.zeros(2, np.int32); rate = np.zeros(8, np.float64)
+    P.lib.x265amd_sao_rdo.argtypes = None
+    assert P.lib.x265amd_sao_rdo(_ptr(c["si"]), c["referenced"], 2, 0, 69, _ptr(c["cu_units"].copy()), _ptr(cnt), _ptr(org), _ptr(rate), _ptr(params), _ptr(flags)) == 0
+    F = [np.full_like(p, c["poison"]) for p in c["rec"]]
+    O.lib.orc_sao_apply_picture(_ptr(_plane_ptrs(D, c["org"])), _ptr(_plane_ptrs(F, c["org"])), C.c_int64(c["stride"]), C.c_int64(c["cstride"]), w, h, _ptr(params))
+    mx, my = c["margin"]
+    for k, f in enumerate(F):
+        sh = 1 if k else 0
+        O.lib.orc_extend_pic_border(off(f.reshape(-1), c["org"][1 if k else 0]), C.c_int64(c["cstride"] if k else c["stride"]), w >> sh, h >> sh, mx >> sh, my >> sh)
+    return dict(D=D, count=cnt, org=org, params=params, F=F)

@@ -593,23 +593,21 @@ int x265amd_encoder::filterRowsCols(Pic& pic, const x265amd_slice_info& si, cons
     static const int minChunkEnv = getenv("X265AMD_FILTER_CHUNK") ? atoi(getenv("X265AMD_FILTER_CHUNK")) : 0;
     const int minChunk = pic.type == TYPE_B ? ctuW : (minChunkEnv > 0 ? minChunkEnv : 2);
     /* the last rows are where a chain of pictures waits for each other (they finish last, and cut CTUs make the last row the slowest): every CTU of them at once */
-    auto minChunkOf = [&](int r) { return (pic.type != TYPE_B && r >= ctuH - 3) ? 1 : minChunk; };
-    std::vector<int> doneTop((size_t)ctuH, 0), doneFull((size_t)ctuH, 0), pubX((size_t)ctuH, 0), a((size_t)ctuH, 0);
+    const int minChunkLast = pic.type != TYPE_B ? 1 : minChunk;
+    /* which chunks a snapshot of the analysis allows, in which order, and what is final behind them: x265amd_filter_plan (host/filter_plan.cpp) */
+    std::vector<int32_t> doneTop((size_t)ctuH, 0), doneFull((size_t)ctuH, 0), pubX((size_t)ctuH, 0), a((size_t)ctuH, 0);
     std::vector<uint8_t> carry((size_t)ctuH * (X265AMD_CTX_STRIDE + 8), 0);
-    struct Unit { int r, c0, c1; };
-    std::vector<Unit> todoTop, todoFull;
+    std::vector<x265amd_filter_step> steps((size_t)2 * ctuH);
+    std::vector<x265amd_filter_finish> finish((size_t)ctuH);
     int rc = X265AMD_OK;
-    /* offsets and borders of the sample columns [pubX[k], newX) of CTU row k (enqueued; published behind the sweep's synchronisation) */
-    auto finishCols = [&](int k, int newX) -> int {
-        const int x0 = pubX[k];
-        if (newX <= x0) return X265AMD_OK;
-        const int y0 = k * 64, y1 = std::min(H, y0 + 64);
+    /* offsets and borders of a finish range (enqueued; published behind the sweep's synchronisation) */
+    auto finishCols = [&](const x265amd_filter_finish& f) -> int {
         if (sao)
         {
-            int r = x265amd_sao_apply_rows_cols(st, recP, finP, stride, cstride, W, H, parCopy ? (const x265amd_sao_ctu*)dPar.p : (const x265amd_sao_ctu*)hPar.p, k, k + 1, x0, newX);
+            int r = x265amd_sao_apply_rows_cols(st, recP, finP, stride, cstride, W, H, parCopy ? (const x265amd_sao_ctu*)dPar.p : (const x265amd_sao_ctu*)hPar.p, f.row, f.row + 1, f.x_begin, f.x_end);
             if (r != X265AMD_OK) return r;
         }
-        return xa_extend_border_band_420(st, fin + org[0], fin + org[1], fin + org[2], stride, cstride, W, H, marginX, marginY, y0, y1, x0, newX, x0 == 0, newX == W);
+        return xa_extend_border_band_420(st, fin + org[0], fin + org[1], fin + org[2], stride, cstride, W, H, marginX, marginY, f.y_begin, f.y_end, f.x_begin, f.x_end, f.x_begin == 0, f.x_end == W);
     };
     /* A CTU row's unit in two steps (round 4).  TOP: the vertical edges of the row's first eight lines and its top horizontal edge -- which completes the deblocking of
      * the row ABOVE -- as soon as the row itself is analysed (nothing of this touches the row's last line, which the row below still reads unfiltered); the row above can
@@ -617,36 +615,13 @@ int x265amd_encoder::filterRowsCols(Pic& pic, const x265amd_slice_info& si, cons
      * edges, the statistics and the decisions, when the row below is analysed (FrameEncoder::m_filterRowDelay).  Vertical edges are decided per four lines and touch only
      * their own lines, the top horizontal edge touches lines 0-2: the samples are those of the reference's order (X265AMD_FILTER_EARLY_TOP=0: both steps together). */
     static const bool earlyTop = !(getenv("X265AMD_FILTER_EARLY_TOP") && atoi(getenv("X265AMD_FILTER_EARLY_TOP")) == 0);
-    auto colsOf = [&](const std::vector<int>& an, int r) -> int { return an[r] == ctuW ? ctuW : an[r] - 1; };
-    auto limTop = [&](const std::vector<int>& an, int r) -> int {
-        int lim = colsOf(an, r);
-        if (r > 0) lim = std::min(lim, doneFull[r - 1]);
-        if (!earlyTop && r + 1 < ctuH) lim = std::min(lim, colsOf(an, r + 1));
-        return lim;
-    };
-    auto limFull = [&](const std::vector<int>& an, int r) -> int {
-        int lim = doneTop[r];
-        if (r + 1 < ctuH) lim = std::min(lim, colsOf(an, r + 1));
-        return lim;
-    };
-    auto chunkOk = [&](int r, int c0, int c1) { return c1 > c0 && (c1 == ctuW || c1 - c0 >= minChunkOf(r)); };
     for (;;)
     {
         {
             std::unique_lock<std::mutex> lk(pic.mu);
             /* something to do? (a snapshot of the analysis: the rows only advance) */
             auto ready = [&]() -> bool {
-                if (pic.failed) return true;
-                bool allDone = true;
-                for (int r = 0; r < ctuH; r++)
-                {
-                    if (doneFull[r] == ctuW) continue;
-                    allDone = false;
-                    if (chunkOk(r, doneTop[r], limTop(pic.analysedCols, r))) return true;
-                    /* (a FULL step may become possible through the TOP step of the same sweep: the TOP test above covers that case) */
-                    if (chunkOk(r, doneFull[r], limFull(pic.analysedCols, r))) return true;
-                }
-                return allDone;
+                return pic.failed || x265amd_filter_ready(W, H, pic.analysedCols.data(), doneTop.data(), doneFull.data(), minChunk, minChunkLast, earlyTop) != 0;
             };
             pic.cv.wait(lk, ready);
             if (pic.failed) return X265AMD_EHIP;
@@ -656,68 +631,61 @@ int x265amd_encoder::filterRowsCols(Pic& pic, const x265amd_slice_info& si, cons
         /* ---- one sweep: every step that is ready, top row first (the stream orders them: FULL of row r - 1, TOP of row r, FULL of row r).  First the edges and the
          * statistics of all of them, one synchronisation, then the decisions on the host, then offsets + borders, a second synchronisation, then the publication:
          * two waits per sweep however many rows are in flight. ---- */
-        todoTop.clear(); todoFull.clear();
         bool all = true;
+        for (int r = 0; r < ctuH; r++) if (doneFull[r] != ctuW) all = false;
+        int numSteps = 0, numFinish = 0;
+        if (x265amd_filter_plan(W, H, a.data(), doneTop.data(), doneFull.data(), pubX.data(), minChunk, minChunkLast, earlyTop, steps.data(), &numSteps, finish.data(), &numFinish) != X265AMD_OK)
+        { rc = xa_fail(X265AMD_EINVAL, "encoder: filter plan"); break; }
         static const bool dbCopy = getenv("X265AMD_DEBLOCK_UNITS_COPY") && atoi(getenv("X265AMD_DEBLOCK_UNITS_COPY")) != 0;
-        for (int r = 0; r < ctuH && rc == X265AMD_OK; r++)
+        bool anyFull = false;
+        for (int i = 0; i < numSteps && rc == X265AMD_OK; i++)
         {
-            if (doneFull[r] == ctuW) continue;
-            all = false;
-            const int y4b = r * 16, y4e = std::min(h4, y4b + 16), y4t = std::min(y4e, y4b + 2);
+            const x265amd_filter_step& s = steps[i];
+            if (s.kind == X265AMD_FILTER_TOP)
             {
-                const int c0 = doneTop[r], c1 = limTop(a, r);
-                if (chunkOk(r, c0, c1))
-                {
-                    const int x4b = c0 * 16, x4e = std::min(w4, c1 * 16 + 1);       /* + the unit column right of the boundary edge */
-                    if (dbl)
-                    {
-                        /* the edge records of the whole row height (both steps read them) where the kernels read them: mapped memory, no copy */
-                        rc = x265amd_deblock_units_rect(&si, &info, pic.units.data(), pic.motion.data(), dbu, y4b, y4e, x4b, x4e);
-                        if (rc != X265AMD_OK) break;
-                        _mm_sfence();       /* the records went through the write-combining BAR mapping: out of this core's buffers before the launch that reads them */
-                        if (dbCopy && hipMemcpy2DAsync((x265amd_deblock_unit*)dDb.p + (size_t)y4b * w4 + x4b, sizeof(x265amd_deblock_unit) * w4, dbu + (size_t)y4b * w4 + x4b, sizeof(x265amd_deblock_unit) * w4,
-                                             sizeof(x265amd_deblock_unit) * (size_t)(x4e - x4b), (size_t)(y4e - y4b), hipMemcpyHostToDevice, st) != hipSuccess)
-                        { rc = xa_fail(X265AMD_EHIP, "encoder: deblock upload"); break; }
-                        rc = x265amd_deblock_rows_cols(st, recY, recU, recV, stride, cstride, W, H, dbCopy ? (const x265amd_deblock_unit*)dDb.p : dbu, p.deblockingFilterBetaOffset, p.deblockingFilterTCOffset, 0, 0, 0, 3, y4b, y4t, c0, c1);
-                        if (rc != X265AMD_OK) break;
-                    }
-                    todoTop.push_back(Unit{ r, c0, c1 });
-                    doneTop[r] = c1;
-                }
+                if (!dbl) continue;
+                /* the edge records of the whole row height (both steps read them) where the kernels read them: mapped memory, no copy */
+                rc = x265amd_deblock_units_rect(&si, &info, pic.units.data(), pic.motion.data(), dbu, s.y4_begin, s.rec_y4_end, s.rec_x4_begin, s.rec_x4_end);
+                if (rc != X265AMD_OK) break;
+                _mm_sfence();       /* the records went through the write-combining BAR mapping: out of this core's buffers before the launch that reads them */
+                const size_t first = (size_t)s.y4_begin * w4 + s.rec_x4_begin;
+                if (dbCopy && hipMemcpy2DAsync((x265amd_deblock_unit*)dDb.p + first, sizeof(x265amd_deblock_unit) * w4, dbu + first, sizeof(x265amd_deblock_unit) * w4,
+                                     sizeof(x265amd_deblock_unit) * (size_t)(s.rec_x4_end - s.rec_x4_begin), (size_t)(s.rec_y4_end - s.y4_begin), hipMemcpyHostToDevice, st) != hipSuccess)
+                { rc = xa_fail(X265AMD_EHIP, "encoder: deblock upload"); break; }
+                rc = x265amd_deblock_rows_cols(st, recY, recU, recV, stride, cstride, W, H, dbCopy ? (const x265amd_deblock_unit*)dDb.p : dbu, p.deblockingFilterBetaOffset, p.deblockingFilterTCOffset, 0, 0, 0, 3, s.y4_begin, s.y4_end, s.col_begin, s.col_end);
+                if (rc != X265AMD_OK) break;
             }
+            else
             {
-                const int c0 = doneFull[r], c1 = limFull(a, r);
-                if (chunkOk(r, c0, c1))
+                anyFull = true;
+                if (dbl && s.y4_end > s.y4_begin)
                 {
-                    if (dbl && y4e > y4t)
-                    {
-                        rc = x265amd_deblock_rows_cols(st, recY, recU, recV, stride, cstride, W, H, dbCopy ? (const x265amd_deblock_unit*)dDb.p : dbu, p.deblockingFilterBetaOffset, p.deblockingFilterTCOffset, 0, 0, 0, 3, y4t, y4e, c0, c1);
-                        if (rc != X265AMD_OK) break;
-                    }
-                    if (sao)
-                    {
-                        /* every workgroup stores all 160 sums and counts of its (CTU, plane): nothing to clear; the host reads them where the kernel leaves them */
-                        rc = x265amd_sao_stats_rows_cols(st, recP, srcP, stride, cstride, W, H, cnt, orgs, r, r + 1, c0, c1);
-                        if (rc != X265AMD_OK) break;
-                    }
-                    todoFull.push_back(Unit{ r, c0, c1 });
-                    doneFull[r] = c1;
+                    rc = x265amd_deblock_rows_cols(st, recY, recU, recV, stride, cstride, W, H, dbCopy ? (const x265amd_deblock_unit*)dDb.p : dbu, p.deblockingFilterBetaOffset, p.deblockingFilterTCOffset, 0, 0, 0, 3, s.y4_begin, s.y4_end, s.col_begin, s.col_end);
+                    if (rc != X265AMD_OK) break;
+                }
+                if (sao)
+                {
+                    /* every workgroup stores all 160 sums and counts of its (CTU, plane): nothing to clear; the host reads them where the kernel leaves them */
+                    rc = x265amd_sao_stats_rows_cols(st, recP, srcP, stride, cstride, W, H, cnt, orgs, s.row, s.row + 1, s.col_begin, s.col_end);
+                    if (rc != X265AMD_OK) break;
                 }
             }
         }
         if (rc != X265AMD_OK) break;
-        if (todoTop.empty() && todoFull.empty()) { if (all) break; continue; }
-        numUnits += (int)(todoTop.size() + todoFull.size()); numSweeps++;
-        if (sao && !todoFull.empty())
+        if (numSteps == 0) { if (all) break; continue; }
+        numUnits += numSteps; numSweeps++;
+        if (sao && anyFull)
         {
             if (streamWaitPolite(st, ev) != hipSuccess) { rc = xa_fail(X265AMD_EHIP, "encoder: sao statistics"); break; }
-            for (const Unit& u : todoFull)
+            for (int i = 0; i < numSteps; i++)
             {
+                const x265amd_filter_step& u = steps[i];
+                if (u.kind != X265AMD_FILTER_FULL) continue;
                 int32_t flags[2] = { 1, 1 };
-                rc = x265amd_sao_rdo_cols(&si, pic.type != TYPE_B ? 1 : 0, 2, p.qpMin, p.qpMax, pic.units.data(), cnt, orgs, sparams.data(), flags, u.r, u.c0, u.c1,
-                                          carry.data() + (size_t)u.r * (X265AMD_CTX_STRIDE + 8));
+                rc = x265amd_sao_rdo_cols(&si, pic.type != TYPE_B ? 1 : 0, 2, p.qpMin, p.qpMax, pic.units.data(), cnt, orgs, sparams.data(), flags, u.row, u.col_begin, u.col_end,
+                                          carry.data() + (size_t)u.row * (X265AMD_CTX_STRIDE + 8));
                 if (rc != X265AMD_OK) break;
-                const size_t off = (size_t)u.r * ctuW + u.c0, n = (size_t)(u.c1 - u.c0);
+                const size_t off = (size_t)u.row * ctuW + u.col_begin, n = (size_t)(u.col_end - u.col_begin);
                 memcpy((x265amd_sao_ctu*)hPar.p + off, sparams.data() + off, sizeof(x265amd_sao_ctu) * n);
                 _mm_sfence();               /* as for the deblocking records above */
                 if (parCopy && hipMemcpyAsync((x265amd_sao_ctu*)dPar.p + off, (const x265amd_sao_ctu*)hPar.p + off, sizeof(x265amd_sao_ctu) * n, hipMemcpyHostToDevice, st) != hipSuccess)
@@ -725,33 +693,11 @@ int x265amd_encoder::filterRowsCols(Pic& pic, const x265amd_slice_info& si, cons
             }
             if (rc != X265AMD_OK) break;
         }
-        /* final now: the row above a TOP step (its parameters were decided by its own FULL step, in this sweep at the latest), and the last row behind its FULL step --
-         * up to eight samples short of the step's right end */
-        for (const Unit& u : todoTop)
-        {
-            if (u.r == 0) continue;
-            rc = finishCols(u.r - 1, u.c1 == ctuW ? W : 64 * u.c1 - 8);
-            if (rc != X265AMD_OK) break;
-        }
-        if (rc != X265AMD_OK) break;
-        for (const Unit& u : todoFull)
-        {
-            if (u.r != ctuH - 1) continue;
-            rc = finishCols(u.r, u.c1 == ctuW ? W : 64 * u.c1 - 8);
-            if (rc != X265AMD_OK) break;
-        }
+        /* final now: the row above a TOP step (its parameters were decided by its own FULL step, in this sweep at the latest), and the last row behind its FULL step */
+        for (int i = 0; i < numFinish && rc == X265AMD_OK; i++) rc = finishCols(finish[i]);
         if (rc != X265AMD_OK) break;
         if (streamWaitPolite(st, ev) != hipSuccess) { rc = xa_fail(X265AMD_EHIP, "encoder: row filters"); break; }
-        for (const Unit& u : todoTop)
-        {
-            const int newX = u.c1 == ctuW ? W : 64 * u.c1 - 8;
-            if (u.r > 0 && newX > pubX[u.r - 1]) { pubX[u.r - 1] = newX; pic.publish(u.r - 1, newX); }
-        }
-        for (const Unit& u : todoFull)
-        {
-            const int newX = u.c1 == ctuW ? W : 64 * u.c1 - 8;
-            if (u.r == ctuH - 1 && newX > pubX[u.r]) { pubX[u.r] = newX; pic.publish(u.r, newX); }
-        }
+        for (int i = 0; i < numFinish; i++) pic.publish(finish[i].row, finish[i].x_end);
         lap(tWork);
     }
     return rc;

@@ -158,6 +158,12 @@ int xa_extend_border_band_420(void* stream, x265amd_pixel* d_y, x265amd_pixel* d
     return X265AMD_OK;
 }
 
+extern "C" int x265amd_extend_border_band_420(void* stream, x265amd_pixel* d_y, x265amd_pixel* d_u, x265amd_pixel* d_v, intptr_t stride, intptr_t cstride, int width, int height,
+                                              int marginX, int marginY, int y_begin, int y_end, int x_begin, int x_end, int left, int right)
+{
+    return xa_extend_border_band_420(stream, d_y, d_u, d_v, stride, cstride, width, height, marginX, marginY, y_begin, y_end, x_begin, x_end, left, right);
+}
+
 extern "C" int x265amd_weight_plane(void* stream, const x265amd_pixel* d_src, x265amd_pixel* d_dst, intptr_t stride, int width, int height,
                                     int marginX, int marginY, int inputWeight, int inputOffset, int log2WeightDenom)
 {

@@ -34,7 +34,7 @@ typedef struct x265amd_param
     int32_t bEnableRectInter, bEnableAMP, limitModes, limitReferences;
     int32_t bEnableEarlySkip, recursionSkipMode, bIntraInBFrames;
     double psyRd;
-    int32_t searchMethod, subpelRefine, searchRange;       /* X265AMD_ME_* (dia / hex / star), subme, merange */
+    int32_t searchMethod, subpelRefine, searchRange;       /* X265AMD_ME_* (dia / hex / star / full), subme, merange */
     int32_t maxNumMergeCand;
     int32_t bEnableSignHiding, bEnableStrongIntraSmoothing, bEnableTemporalMvp;
     int32_t tuQTMaxInterDepth, tuQTMaxIntraDepth;

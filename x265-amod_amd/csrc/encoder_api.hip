@@ -137,7 +137,7 @@ extern "C" x265amd_encoder* x265amd_encoder_open(const x265amd_param* p)
         XA_REQUIRE(p->maxNumMergeCand >= 1 && p->maxNumMergeCand <= 5, "maxNumMergeCand outside 1..5");
         XA_REQUIRE(p->tuQTMaxInterDepth >= 1 && p->tuQTMaxInterDepth <= 4, "tuQTMaxInterDepth outside 1..4");
         XA_REQUIRE(p->tuQTMaxIntraDepth >= 1 && p->tuQTMaxIntraDepth <= 4, "tuQTMaxIntraDepth outside 1..4");
-        XA_REQUIRE(p->searchMethod == X265AMD_ME_DIA || p->searchMethod == X265AMD_ME_HEX || p->searchMethod == X265AMD_ME_STAR, "searchMethod: only dia, hex and star are built (no umh / sea / full)");
+        XA_REQUIRE(p->searchMethod == X265AMD_ME_DIA || p->searchMethod == X265AMD_ME_HEX || p->searchMethod == X265AMD_ME_STAR || p->searchMethod == X265AMD_ME_FULL, "searchMethod: only dia, hex, star and full are built (no umh / sea)");
         XA_REQUIRE(p->subpelRefine >= 0 && p->subpelRefine <= 7, "subpelRefine outside 0..7");
         XA_REQUIRE(p->rdoqLevel >= 0 && p->rdoqLevel <= 2, "rdoqLevel outside 0..2");
         XA_REQUIRE(p->psyRdoqFix8 >= 0, "psyRdoqFix8 negative");

@@ -324,7 +324,7 @@ extern "C" int x265amd_pred_inter_search_ex(x265amd_me_ctx* me, void* stream, co
                 for (int k = 0; k < ng; k++) { g[k].first_job += (int)ordered.size(); groups.push_back(g[k]); maxW = g[k].win_w > maxW ? g[k].win_w : maxW; maxH = g[k].win_h > maxH ? g[k].win_h : maxH; }
                 for (size_t k = 0; k < sub.size(); k++) { ordered.push_back(sub[order[k]]); origin.push_back(idx[order[k]]); }
             }
-            for (const x265amd_me_job& j : mj) { if ((j.method & 0x7f) == X265AMD_ME_STAR) flags |= X265AMD_ME_FLAG_STAR; if (j.method & X265AMD_ME_CHROMA_SATD) flags |= X265AMD_ME_FLAG_CHROMA; }
+            for (const x265amd_me_job& j : mj) { if ((j.method & 0x7f) == X265AMD_ME_STAR) flags |= X265AMD_ME_FLAG_STAR; if ((j.method & 0x7f) == X265AMD_ME_FULL) flags |= X265AMD_ME_FLAG_FULL; if (j.method & X265AMD_ME_CHROMA_SATD) flags |= X265AMD_ME_FLAG_CHROMA; }
             XaMapped dJ, dG; Dev dO;           /* the results stay in device memory: the deferred pass reads what the first pass left there */
             if (dJ.alloc(ordered.size() * sizeof(x265amd_me_job)) != hipSuccess || dG.alloc(groups.size() * sizeof(x265amd_me_group)) != hipSuccess ||
                 dO.alloc(ordered.size() * sizeof(x265amd_me_result)))

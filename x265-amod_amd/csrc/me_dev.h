@@ -738,6 +738,108 @@ template<bool SLOW> __device__ __noinline__ void me_star_pattern(int sOff, int& 
     }
 }
 
+/* ---- exhaustive search (X265_FULL_SEARCH, motion.cpp:1422-1466) ----
+ * The reference prices every full-pel vector of [mvmin.y, mvmax.y] x [mvmin.x, mvmax.x] in raster order (y outer, x inner) as
+ * sad + mvcost and keeps a vector on strict `<`: it ends with the lexicographic minimum of (cost, y, x) over the area when
+ * that cost is below what the predictor stage left, and with the predictor stage's vector otherwise.  No candidate depends
+ * on another, so the scan is turned round against the other searches: ONE LANE PER CANDIDATE, every wavefront of the
+ * workgroup on the same job, and a single reduction of the 64-bit key (cost << 32 | y-index << 16 | x-index) per job
+ * (cost < 2^23; both indices < 2^16 for any int16 bounds; no raster index is ever formed).  Neighbouring lanes take
+ * neighbouring x: a wavefront's window reads fall on consecutive dwords.  A candidate whose block leaves the staged window
+ * (or every candidate, win == NULL: the direct-from-HBM pass) reads the reference plane instead -- same arithmetic.
+ * The workgroup leaves the winning vector in the job's result record (mv only; `cost` is not touched: the deferred pass
+ * keeps its marker there) and me_search's case X265AMD_ME_FULL prices that one vector again and compares it with bcost.
+ * Called by all `nthr` threads; `redOff` is the LDS byte offset of the first wavefront's MeState (acc[] holds the wavefronts' keys). */
+__device__ __noinline__ void me_full_scan(const x265amd_me_job* __restrict__ jp, x265amd_me_result* out, const pixel* win, int winX, int winY, int winW, int winH,
+                                          const pixel* fencT, int fencX, int fencY, const pixel* refG, int stride, const uint16_t* tables, int redOff, int tid, int nthr)
+{
+    const int px = jp->x, py = jp->y, w = jp->w, h = jp->h, gpr = w >> 2;
+    const int mnx = jp->mvmin[0], mny = jp->mvmin[1];
+    const int W = jp->mvmax[0] - mnx + 1, H = jp->mvmax[1] - mny + 1;
+    const int fx = px - fencX, fy = py - fencY;
+    const int padR = XA_DEPTH == 8 ? 4 : 0;     /* the dword reads of the 8-bit LDS path touch up to 3 samples past the block's right edge */
+    uint64_t best = ~0ull;
+    if (W > 0 && H > 0)
+    {
+        const uint16_t* cost = tables + (size_t)jp->qp * ME_TBL_LEN + ME_TBL_HALF;
+        const int mvpx = jp->mvp[0], mvpy = jp->mvp[1];
+        const int dx = nthr % W, dy = nthr / W;
+        int xi = tid % W, yi = tid / W;
+        while (yi < H)
+        {
+            const int mx = mnx + xi, my = mny + yi, X = px + mx, Y = py + my;
+            int sum = 0;
+            if (win && X >= winX && Y >= winY && X + w + padR <= winX + winW && Y + h <= winY + winH)
+            {
+#if XA_DEPTH == 8
+                const int o = (Y - winY) * winW + (X - winX), sh = o & 3;      /* winW % 4 == 0: one byte shift for every row */
+                const uint32_t* wp = reinterpret_cast<const uint32_t*>(win) + (o >> 2);
+                const uint32_t* fp = reinterpret_cast<const uint32_t*>(fencT) + fy * 16 + (fx >> 2);
+                for (int y = 0; y < h; y++, wp += winW >> 2, fp += 16)
+                {
+                    uint32_t lo = wp[0];
+                    for (int k = 0; k < gpr; k++)
+                    {
+                        const uint32_t hi = wp[k + 1];
+                        sum = __builtin_amdgcn_sad_u8(fp[k], __builtin_amdgcn_alignbyte(hi, lo, sh), sum);
+                        lo = hi;
+                    }
+                }
+#else
+                const pixel* wp = win + (Y - winY) * winW + (X - winX);
+                const pixel* fp = fencT + fy * 64 + fx;
+                for (int y = 0; y < h; y++, wp += winW, fp += 64)
+                    for (int x = 0; x < w; x++) sum += abs((int)fp[x] - (int)wp[x]);
+#endif
+            }
+            else
+            {
+                const pixel* rp = refG + (long)Y * stride + X;
+                const pixel* fp = fencT + fy * 64 + fx;
+                for (int y = 0; y < h; y++, rp += stride, fp += 64)
+                    for (int k = 0; k < gpr; k++)
+                    {
+                        pixel r[4], f[4];
+                        __builtin_memcpy(r, rp + 4 * k, sizeof(r));
+                        __builtin_memcpy(f, fp + 4 * k, sizeof(f));
+#pragma unroll
+                        for (int x = 0; x < 4; x++) sum += abs((int)f[x] - (int)r[x]);
+                    }
+            }
+            const int c = sum + (int)(uint16_t)(cost[4 * mx - mvpx] + cost[4 * my - mvpy]);
+            const uint64_t key = ((uint64_t)(uint32_t)c << 32) | ((uint32_t)yi << 16) | (uint32_t)xi;
+            best = key < best ? key : best;
+            xi += dx; yi += dy;
+            if (xi >= W) { xi -= W; yi++; }
+        }
+    }
+    for (int m = 32; m; m >>= 1)
+    {
+        const uint64_t o = ((uint64_t)(uint32_t)__shfl_xor((int)(best >> 32), m, 64) << 32) | (uint32_t)__shfl_xor((int)(uint32_t)best, m, 64);
+        best = o < best ? o : best;
+    }
+    const int nwv = nthr >> 6;
+    if ((tid & 63) == 0)
+    {
+        uint32_t* red = reinterpret_cast<uint32_t*>(me_smem + redOff + (tid >> 6) * (int)sizeof(MeState) + offsetof(MeState, acc));
+        red[0] = (uint32_t)best; red[1] = (uint32_t)(best >> 32);
+    }
+    __syncthreads();
+    if (tid == 0)
+    {
+        for (int k = 1; k < nwv; k++)
+        {
+            const uint32_t* red = reinterpret_cast<const uint32_t*>(me_smem + redOff + k * (int)sizeof(MeState) + offsetof(MeState, acc));
+            const uint64_t o = ((uint64_t)red[1] << 32) | red[0];
+            best = o < best ? o : best;
+        }
+        if (best != ~0ull)      /* read back by another wavefront (me_search): past this compute unit's vector cache, like the load there */
+            __hip_atomic_store(reinterpret_cast<int*>(out->mv), ME_PK(mnx + (int)(best & 0xffff), mny + (int)((best >> 16) & 0xffff)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __threadfence();
+    }
+    __syncthreads();
+}
+
 /* MotionEstimate::motionEstimate: motion.cpp:764-1594 (full-resolution reference, one slice, luma only) */
 /* `jp` points at the job record in HBM: its fields are wave-uniform scalar loads (a by-value copy would live in scratch
  * because mvc[] is indexed dynamically -- measured as 457 MB of scratch writes per 1080p launch) */
@@ -945,7 +1047,23 @@ template<bool SLOW, bool STAR> __device__ void me_search(int sOff, const x265amd
         ME_OOB(sOff);       /* this kernel variant was built without the star search: redo in k_me_deferred */
         break;
     }
-    default:    /* UMH / SEA / FULL are not implemented: flagged, never silently replaced */
+    /* motion.cpp:1422-1466: the workgroup's scan (me_full_scan) has left the area's first cheapest vector in the result record.  Only the variants that carry the
+     * star search have this case; in the HEX/DIA variant a FULL job takes the default branch, and block_me_deferred redoes a FULL job that is marked -1 (me_redo) */
+    case X265AMD_ME_FULL:
+    if constexpr (STAR)
+    {
+        if (s.mnx <= s.mxx && s.mny <= s.mxy)
+        {
+            const int pk = __hip_atomic_load(reinterpret_cast<const int*>(out->mv), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const int fx = (int)(int16_t)(pk & 0xffff), fy = pk >> 16;
+            /* priced from memory: exact wherever the block lies, and one block among the area's thousands */
+            const int c = me_sad_at_w<true>(sOff, fx, fy) + me_mvcost(s, fx * 4, fy * 4);
+            if (c < bcost) { bcost = c; bx = fx; by = fy; }
+        }
+        break;
+    }
+    [[fallthrough]];
+    default:    /* UMH / SEA are not implemented: flagged, never silently replaced (and FULL in the HEX/DIA variant: see above) */
         if (xa_lane() == 0) { out->mv[0] = 0; out->mv[1] = 0; out->cost = -1; }
         return;
     }
@@ -1058,6 +1176,14 @@ template<bool STAR> XA_DEV void block_me_search(const MeParams& p, int vb, int t
         if (tid == 0) *counter = 0;
     }
     __syncthreads();
+    if constexpr (STAR)     /* the group's exhaustive searches first, every wavefront on each */
+        for (int ji = 0; ji < g.num_jobs; ji++)
+        {
+            const x265amd_me_job* jp = p.jobs + g.first_job + ji;
+            if ((jp->method & 0x7f) == X265AMD_ME_FULL)
+                me_full_scan(jp, p.out + g.first_job + ji, win, g.win_x, g.win_y, g.win_w, g.win_h, fencT, g.fenc_x, g.fenc_y, refG, p.stride, p.tables,
+                             (int)(reinterpret_cast<char*>(counter + 4) - smem), tid, nthr);
+        }
 
     const int lane = xa_lane();
     for (;;)
@@ -1114,6 +1240,16 @@ template<bool STAR> XA_DEV void block_me_search_multi(const MeParams& p, int gro
         }
     }
     __syncthreads();
+    if constexpr (STAR)
+        for (int gi = 0; gi < groups; gi++)
+        {
+            const x265amd_me_group g = p.groups[gi];
+            const x265amd_me_job* jp = p.jobs + g.first_job;
+            if ((jp->method & 0x7f) != X265AMD_ME_FULL) continue;
+            const pixel* win = reinterpret_cast<const pixel*>(smem + (size_t)gi * region);
+            me_full_scan(jp, p.out + g.first_job, win, g.win_x, g.win_y, g.win_w, g.win_h, win + p.maxWinW * p.maxWinH + 16, g.fenc_x, g.fenc_y,
+                         reinterpret_cast<const pixel*>(p.refs[g.ref]), p.stride, p.tables, (int)((size_t)groups * region + 16), tid, nthr);
+        }
     if (wv < groups)
     {
         const x265amd_me_group g = p.groups[wv];
@@ -1126,6 +1262,13 @@ template<bool STAR> XA_DEV void block_me_search_multi(const MeParams& p, int gro
         me_search<false, STAR>(sOff, jp, p.out + g.first_job);
         xa_wave_sync();
     }
+}
+
+/* what the direct-from-HBM pass has to do: a job marked ME_DEFERRED, and an exhaustive search that a variant without it has flagged -1 */
+XA_DEV bool me_redo(const MeParams& p, int job)
+{
+    const int c = p.out[job].cost;
+    return c == ME_DEFERRED || (c == -1 && (p.jobs[job].method & 0x7f) == X265AMD_ME_FULL);
 }
 
 /* direct-from-HBM kernel: redoes the jobs the window-resident kernel marked ME_DEFERRED (a candidate left the staged
@@ -1146,7 +1289,7 @@ XA_DEV void block_me_deferred(const MeParams& p, int vb, int tid, int nthr)
     if (tid == 0) *flag = 0;
     __syncthreads();
     int any = 0;
-    for (int i = tid; i < g.num_jobs; i += nthr) any |= p.out[g.first_job + i].cost == ME_DEFERRED;
+    for (int i = tid; i < g.num_jobs; i += nthr) any |= me_redo(p, g.first_job + i);
     if (any) atomicOr(flag, 1);
     __syncthreads();
     if (!*flag) return;
@@ -1158,9 +1301,16 @@ XA_DEV void block_me_deferred(const MeParams& p, int vb, int tid, int nthr)
         __builtin_memcpy(fencT + y * 64 + x, v, sizeof(v));
     }
     __syncthreads();
+    for (int ji = 0; ji < g.num_jobs; ji++)     /* exhaustive searches sent here: scanned from memory by the whole workgroup */
+    {
+        const x265amd_me_job* jp = p.jobs + g.first_job + ji;
+        if ((jp->method & 0x7f) == X265AMD_ME_FULL && me_redo(p, g.first_job + ji))
+            me_full_scan(jp, p.out + g.first_job + ji, nullptr, 0, 0, 0, 0, fencT, g.fenc_x, g.fenc_y, refG, p.stride, p.tables,
+                         (int)(reinterpret_cast<char*>(flag + 4) - smem), tid, nthr);
+    }
     for (int ji = wv; ji < g.num_jobs; ji += nwv)
     {
-        if (p.out[g.first_job + ji].cost != ME_DEFERRED) continue;
+        if (!me_redo(p, g.first_job + ji)) continue;
         const x265amd_me_job* jp = p.jobs + g.first_job + ji;
         if (lane == 0) me_set_job(s, *jp, g, p, nullptr, 0, 0, fencT, refG);
         xa_wave_sync();

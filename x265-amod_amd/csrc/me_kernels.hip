@@ -1,7 +1,8 @@
 /* Layer 3: motion estimation on device-resident pictures (include/x265amd.h, `x265amd_me_*`).
  *
  * Device restatement of the reference's MotionEstimate::motionEstimate() (source/encoder/motion.cpp:764-1594) with
- * its DIA, HEX and STAR integer searches (StarPatternSearch, motion.cpp:387-629), the sub-pel refinement driven by
+ * its DIA, HEX, STAR and FULL integer searches (StarPatternSearch, motion.cpp:387-629; the exhaustive search,
+ * motion.cpp:1422-1466), the sub-pel refinement driven by
  * the `workload` table (motion.cpp:48-58), subpelCompare's luma path (motion.cpp:1596-1623) and BitCost's MV cost
  * tables (source/encoder/bitcost.cpp:30-109).  Integer arithmetic throughout: results (quarter-pel MV and cost) are
  * bit-exact with the reference for the same arguments.
@@ -10,6 +11,9 @@
  * and its 64x64 source tile are staged in LDS with coalesced row reads; each 64-lane wavefront pulls jobs from an
  * LDS counter and runs the (data dependent, serial) search for its job with all candidates' SAD/SATD sums reduced
  * across the wavefront.  8-bit SADs use v_sad_u8 on dwords assembled from the LDS window with v_alignbyte.
+ * The exhaustive search has no serial chain and is mapped the other way round (me_full_scan, me_dev.h): before the
+ * wavefronts pull jobs, the whole workgroup scans each FULL job's area with one candidate per lane and one 64-bit
+ * (cost, y, x) minimum per job; the job's wavefront then continues from that vector like every other method.
  */
 #include <math.h>
 #include <algorithm>
@@ -167,7 +171,7 @@ extern "C" int x265amd_me_search(x265amd_me_ctx* ctx, void* stream, const x265am
     const int waves = queue ? XA_SERVER_WAVES : ME_WAVES;
     size_t lds = ((size_t)max_win_w * max_win_h + 16 + 64 * 64) * sizeof(pixel) + 16 + waves * sizeof(MeState);
     if (lds > (queue ? (size_t)XA_SERVER_LDS : (size_t)160 * 1024)) return xa_fail(X265AMD_EINVAL, "x265amd_me_search: window does not fit the LDS");
-    const bool star = (flags & (X265AMD_ME_FLAG_STAR | X265AMD_ME_FLAG_CHROMA)) != 0;   /* the variant with star search + chroma SATD */
+    const bool star = (flags & (X265AMD_ME_FLAG_STAR | X265AMD_ME_FLAG_CHROMA | X265AMD_ME_FLAG_FULL)) != 0;   /* the variant with star + exhaustive search + chroma SATD */
     if ((flags & X265AMD_ME_FLAG_CHROMA) && !d_chroma) return xa_fail(X265AMD_EINVAL, "x265amd_me_search: X265AMD_ME_FLAG_CHROMA without chroma planes");
     static thread_local size_t configured[2] = { 0, 0 };
     if (!queue && lds > configured[star])

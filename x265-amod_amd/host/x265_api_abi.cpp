@@ -383,7 +383,7 @@ void* abi_encoder_open(void* p)
     REQUIRE(!PI(p, bDistributeModeAnalysis) && !PI(p, bDistributeMotionEstimation), "pmode / pme are not built");
     REQUIRE(!PI(p, bAQMotion) && !PI(p, gopLookahead) && !PI(p, radl) && !PI(p, bEnableSceneCutAwareQp) && !PI(p, bEnableFades), "aq-motion / gop-lookahead / radl / scenecut-aware-qp / fades are not built");
     REQUIRE(PI(p, levelIdc) == 0, "levelIdc: the level is derived (determineLevel), not forced");
-    REQUIRE(PI(p, searchMethod) == 0 || PI(p, searchMethod) == 1 || PI(p, searchMethod) == 3, "searchMethod: only dia, hex and star are built");
+    REQUIRE(PI(p, searchMethod) == 0 || PI(p, searchMethod) == 1 || PI(p, searchMethod) == 3 || PI(p, searchMethod) == 5, "searchMethod: only dia, hex, star and full are built (no umh / sea)");
 #undef REQUIRE
     if (bad) { snprintf(why, sizeof(why), "x265_encoder_open: %s", bad); xa_fail(X265AMD_EINVAL, why); return nullptr; }
     x265amd_param q;

@@ -1133,10 +1133,35 @@ int x265amd_aq_energy(void* stream, const uint64_t planes[3], intptr_t stride, i
 /* x265amd_aq_offsets = the rest of LookaheadTLD::calcAdaptiveQuantFrame (reference: source/encoder/slicetype.cpp:513-640), host code: the energies of
  * x265amd_aq_energy -> Lowres::qpAqOffset, qpCuTreeOffset (doubles) and invQscaleFactor (x265_exp2fix8) per quantisation group, for aq_mode 1 (variance),
  * 2 (auto-variance), 3 (auto-variance biased); aq_strength / aq_bias_strength = param.rc.aqStrength / aqBiasStrength.  No HDR10 offsets, external quant
- * offsets, hevc-aq or edge modes.  num_blocks: the groups of x265amd_aq_energy; avg_block_count: the count the reference averages over (lowres widthInCU x
+ * offsets or hevc-aq; the edge modes 4 and 5 take two more arrays and have an entry of their own, x265amd_aq_offsets_edge below (this one returns
+ * X265AMD_EINVAL for them).  num_blocks: the groups of x265amd_aq_energy; avg_block_count: the count the reference averages over (lowres widthInCU x
  * heightInCU, x 4 for qg 8; equal to num_blocks when the picture size is a multiple of 16).  Returns X265AMD_OK or X265AMD_EINVAL. */
 int x265amd_aq_offsets(const uint32_t* energy, int num_blocks, int avg_block_count, int aq_mode, double aq_strength, double aq_bias_strength, int qg_size,
                        double* qp_aq_offset, double* qp_cutree_offset, int32_t* inv_qscale_factor);
+
+/* The edge-based modes (--aq-mode 4: X265_AQ_EDGE, 5: X265_AQ_EDGE_BIASED).
+ * x265amd_aq_edge = edgeFilter + computeEdge + LookaheadTLD::edgeDensityCu for every 16x16 block of a source picture (reference: source/encoder/slicetype.cpp:98-261):
+ * a 5x5 Gaussian of the luma plane (the two outermost rows and columns keep the source), a 3x3 Sobel of that, per sample the angle of the gradient in degrees
+ * (0..180) and the edge decision (the largest sample value where the gradient's magnitude reaches it, else 0; on the picture's outermost row and column the edge
+ * picture keeps the SOURCE sample and the angle is 0; both are 0 beyond the picture).  d_density[block] = the variance of the edge picture over the block
+ * (ssd - (sum * sum >> 8)), d_avg_angle[block] = the sum of the angles / 256; raster order, ceil(width / 16) blocks per row.  d_wp[0] += the edge picture's sum,
+ * d_wp[1] += its sum of squares: the reference adds both to Lowres::wp_sum[0] / wp_ssd[0], on top of the source's (x265amd_aq_energy's d_wp[0] and d_wp[3]).
+ * luma: device address of sample (0,0); only samples inside width x height are read.  edge_plane / theta_plane: 0, or device addresses of width x height samples
+ * (no padding) that receive the two pictures.  qg_size: 16.  Asynchronous. */
+int x265amd_aq_edge(void* stream, uint64_t luma, intptr_t stride, int width, int height, int qg_size, uint32_t* d_density, uint32_t* d_avg_angle, uint64_t* d_wp,
+                    uint64_t edge_plane, uint64_t theta_plane);
+
+/* x265amd_aq_offsets for aq_mode 4 and 5 (reference: source/encoder/slicetype.cpp:537-650), host code: a block's first-pass value comes from its edge density where
+ * that is not zero, else from its energy; a block whose mean angle lies in 30..60 or 120..150 and whose value is above the picture's average gets strength + 0.5;
+ * mode 5 adds a tenth of mode 3's bias to dark scenes.  energy: x265amd_aq_energy's; density, avg_angle: x265amd_aq_edge's.  qg_size: 16. */
+int x265amd_aq_offsets_edge(const uint32_t* energy, const uint32_t* density, const uint32_t* avg_angle, int num_blocks, int avg_block_count, int aq_mode,
+                            double aq_strength, double aq_bias_strength, int qg_size, double* qp_aq_offset, double* qp_cutree_offset, int32_t* inv_qscale_factor);
+
+/* The angle (0..180) and the edge decision (0 or the largest sample) x265amd_aq_edge gives a sample whose Sobel gradients are gv[i], gh[i] (|g| < 2^15): the host's copy
+ * and the device's (asynchronous; device arrays) of ONE function that uses no maths library (csrc/aq_edge_dev.h), so that the two can be held against each other and
+ * the host's against the reference's arithmetic over every pair (tests/native/aq_theta_check.cpp). */
+int x265amd_aq_edge_angles(const int32_t* gv, const int32_t* gh, int count, int32_t* theta, int32_t* edge);
+int x265amd_aq_edge_angles_device(void* stream, const int32_t* d_gv, const int32_t* d_gh, int count, int32_t* d_theta, int32_t* d_edge);
 
 /* returns the device scratch the host orchestrators keep between calls (a size-class pool) to the HIP runtime */
 void x265amd_release_scratch(void);

@@ -100,7 +100,8 @@ typedef struct x265amd_param
     double rfConstant;                      /* param.rc.rfConstant (--crf; 28) */
     double aqStrength;                      /* param.rc.aqStrength (--aq-strength; 1.0) */
     double qCompress;                       /* param.rc.qCompress (--qcomp; 0.6): cuTree's strength 5 (1 - qcomp) and, without cuTree, the exponent of the blurred complexity */
-    int32_t aqMode;                         /* param.rc.aqMode (--aq-mode): 0 off, 1 variance, 2 auto-variance (the default), 3 auto-variance biased to dark scenes
+    int32_t aqMode;                         /* param.rc.aqMode (--aq-mode): 0 off, 1 variance, 2 auto-variance (the default), 3 auto-variance biased to dark scenes,
+                                             * 4 edge-based, 5 edge-based biased to dark scenes (not with recursionSkipMode 2)
                                              * (LookaheadTLD::calcAdaptiveQuantFrame, slicetype.cpp:452-713): a QP offset per 16x16 block, the QP of a CU = the picture's
                                              * QP + the mean offset of the blocks under its quantisation group (Analysis::calculateQpforCuSize, analysis.cpp:3634-3714),
                                              * cu_qp_delta in the stream (pps.cu_qp_delta_enabled_flag, diff_cu_qp_delta_depth from qgSize) */

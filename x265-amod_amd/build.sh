@@ -33,7 +33,8 @@ build_one() {
         # fm_*.cpp: double-precision arithmetic that has to come out like the reference's, which is compiled -O2 -ffast-math (source/CMakeLists.txt:226-240)
         local fm=""
         case "$(basename "$f")" in fm_*) fm="-ffast-math";; esac
-        g++ -O2 $fm -std=c++17 -fPIC -Wall -I"$HERE/../include" -DX265AMD_DEPTH=$depth -c "$f" -o "$o" &
+        # (-ffp-contract=off: csrc/aq_edge_dev.h must give the device's bits whatever the target -- no fused multiply-add from a product and a sum)
+        g++ -O2 $fm -ffp-contract=off -std=c++17 -fPIC -Wall -I"$HERE/../include" -DX265AMD_DEPTH=$depth -c "$f" -o "$o" &
         pids="$pids $!"
         objs="$objs $o"
     done

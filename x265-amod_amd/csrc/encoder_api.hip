@@ -118,7 +118,7 @@ extern "C" x265amd_encoder* x265amd_encoder_open(const x265amd_param* p)
         XA_REQUIRE(p->rateControlMode == 0 || p->rateControlMode == X265AMD_RC_CQP || p->rateControlMode == X265AMD_RC_CRF, "rc.rateControlMode: constant QP (1) and constant rate factor (2) are built, ABR (0 with a bitrate) is not");
         XA_REQUIRE(p->rateControlMode == X265AMD_RC_CRF || (p->qp >= 0 && p->qp <= 51), "qp outside 0..51");
         XA_REQUIRE(p->rateControlMode != X265AMD_RC_CRF || (p->rfConstant >= 0 && p->rfConstant <= 51), "rfConstant outside 0..51");
-        XA_REQUIRE(p->aqMode >= 0 && p->aqMode <= 3, "aqMode outside 0..3 (the edge-based modes are not built)");
+        XA_REQUIRE(p->aqMode >= 0 && p->aqMode <= 5, "aqMode outside 0..5");
         XA_REQUIRE(p->qpMin >= 0 && p->qpMin <= p->qpMax && p->qpMax <= 69, "qpMin / qpMax outside 0..69 (or crossed)");
         XA_REQUIRE(p->aspectRatioIdc >= 0 && (p->aspectRatioIdc <= 16 || p->aspectRatioIdc == 255), "aspectRatioIdc outside 0..16 / 255");
         XA_REQUIRE(p->deblockingFilterTCOffset >= -6 && p->deblockingFilterTCOffset <= 6 && p->deblockingFilterBetaOffset >= -6 && p->deblockingFilterBetaOffset <= 6, "deblocking offsets outside -6..6");

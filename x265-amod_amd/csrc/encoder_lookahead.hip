@@ -44,7 +44,13 @@ int x265amd_encoder::lowresInit(Pic& pic)
         const int bw = (W + 15) / 16, bh = (H + 15) / 16, nb = bw * bh;
         pic.qpAqOffset.assign((size_t)nb, 0.0); pic.qpCuTreeOffset.assign((size_t)nb, 0.0); pic.invQscale.assign((size_t)nb, 256);
         /* (strength 0 -- cuTree without adaptive quantisation, --tune psnr: the arrays stay zero / 256, slicetype.cpp:483-505; the energies were only needed for the picture's sums) */
-        if (p.aqStrength != 0)
+        if (p.aqStrength != 0 && p.aqMode >= 4)
+        {
+            /* the edge modes: densities and mean angles lie behind the energies and the six sums (adaptiveQuant) */
+            const uint32_t* density = (const uint32_t*)((const char*)aqEnergyHost + (size_t)nb * 4 + 6 * 8);
+            rc = x265amd_aq_offsets_edge((const uint32_t*)aqEnergyHost, density, density + nb, nb, lowCuW * lowCuH, p.aqMode, p.aqStrength, 1.0, 16, pic.qpAqOffset.data(), pic.qpCuTreeOffset.data(), pic.invQscale.data());
+        }
+        else if (p.aqStrength != 0)
             rc = x265amd_aq_offsets((const uint32_t*)aqEnergyHost, nb, lowCuW * lowCuH, p.aqMode, p.aqStrength, 1.0, 16, pic.qpAqOffset.data(), pic.qpCuTreeOffset.data(), pic.invQscale.data());
         if (rc != X265AMD_OK) return xa_fail(rc, "encoder_encode: adaptive quantisation");
         pic.intraCostHost = ic;
@@ -73,18 +79,30 @@ int x265amd_encoder::lowresInit(Pic& pic)
 }
 
 /* LookaheadTLD::calcAdaptiveQuantFrame's block loop (slicetype.cpp:560-600): acEnergyCu of every 16x16 block (luma + both chroma blocks) and the picture's sums for the weight
- * analysis, enqueued on the lookahead's stream with their read-back; the caller waits for the stream once (lowresInit) and turns the energies into offsets */
+ * analysis -- under the edge modes edgeDensityCu of every block as well --, enqueued on the lookahead's stream with their read-back; the caller waits for the stream once (lowresInit) and turns the energies into offsets */
 int x265amd_encoder::adaptiveQuant(Pic& pic)
 {
     const int bw = (W + 15) / 16, bh = (H + 15) / 16;
     const size_t nb = (size_t)bw * bh;
-    if (!aqEnergy && (xa_scratch_alloc(&aqEnergy, nb * 4) != hipSuccess || xa_scratch_alloc(&aqSums, 6 * 8) != hipSuccess || xa_mapped_alloc(&aqEnergyHost, nb * 4 + 6 * 8, true) != hipSuccess))
+    /* (the edge modes, aqMode 4 and 5: two more words per block, edge density and mean angle) */
+    const bool edge = p.aqMode >= 4 && p.aqStrength != 0;
+    const size_t perBlock = edge ? 12 : 4;
+    if (!aqEnergy && (xa_scratch_alloc(&aqEnergy, nb * perBlock) != hipSuccess || xa_scratch_alloc(&aqSums, 6 * 8) != hipSuccess || xa_mapped_alloc(&aqEnergyHost, nb * perBlock + 6 * 8, true) != hipSuccess))
         return xa_fail(X265AMD_EHIP, "encoder_encode: device allocation");
     if ((p.bEnableWeightedPred || p.bEnableWeightedBiPred) && !wpMvs && xa_mapped_alloc(&wpMvs, (size_t)lowCuW * lowCuH * 4, false) != hipSuccess)
         return xa_fail(X265AMD_EHIP, "encoder_encode: device allocation");
     const uint64_t srcP[3] = { planeAddr(pic.dSrc, 0), planeAddr(pic.dSrc, 1), planeAddr(pic.dSrc, 2) };
     int rc = x265amd_aq_energy(laStream, srcP, stride, cstride, W, H, 16, (uint32_t*)aqEnergy, (uint64_t*)aqSums);
     if (rc != X265AMD_OK) return rc;
+    if (edge)
+    {
+        /* edgeFilter + edgeDensityCu (slicetype.cpp:527-548); the edge picture's sums are added to the source's luma sums, as acEnergyVar does */
+        uint32_t* density = (uint32_t*)aqEnergy + nb;
+        rc = xa_aq_edge(laStream, srcP[0], stride, W, H, 16, density, density + nb, (uint64_t*)aqSums, (uint64_t*)aqSums + 3, 0, 0);
+        if (rc != X265AMD_OK) return rc;
+        if (hipMemcpyAsync((char*)aqEnergyHost + nb * 4 + 6 * 8, density, nb * 8, hipMemcpyDeviceToHost, laStream) != hipSuccess)
+            return xa_fail(X265AMD_EHIP, "encoder_encode: edge densities");
+    }
     if (hipMemcpyAsync(aqEnergyHost, aqEnergy, nb * 4, hipMemcpyDeviceToHost, laStream) != hipSuccess ||
         hipMemcpyAsync((char*)aqEnergyHost + nb * 4, aqSums, 6 * 8, hipMemcpyDeviceToHost, laStream) != hipSuccess)
         return xa_fail(X265AMD_EHIP, "encoder_encode: block energies");

@@ -866,3 +866,135 @@ extern "C" int x265amd_aq_energy(void* stream, const uint64_t planes[3], intptr_
     if (e != hipSuccess) return xa_fail(X265AMD_EHIP, hipGetErrorString(e));
     return X265AMD_OK;
 }
+
+/* ---------------- adaptive quantisation, the edge-based modes (--aq-mode 4 / 5): edgeFilter + computeEdge + edgeDensityCu for every 16x16 block ----------------
+ * (slicetype.cpp:98-261).  Per picture: a 5x5 Gaussian of the source (inside a border of two samples, which keeps the source), a 3x3 Sobel of that (inside a border of
+ * one sample, where the edge picture keeps the SOURCE sample and the angle is 0; both are 0 beyond the picture, which the blocks of a size that is no multiple of 16
+ * read), the angle and the edge decision per sample (aq_edge_dev.h), then per block the variance of the edge picture and the mean angle, and the edge picture's sum
+ * and sum of squares for the picture (acEnergyVar adds them to Lowres::wp_sum[0] / wp_ssd[0]).
+ * One workgroup per tile of 4 x 1 blocks (64 x 16 samples), one wavefront per block: the source tile with a halo of 3 and the Gaussian tile with a halo of 1 live in
+ * LDS, so that a source sample is read from memory 1.5 times on average; the block sums are wave reductions; the picture's sums go through per-block partial sums and a
+ * second small kernel, as k_aq_energy's do.  Integer and float VALU plus ~40 double operations per sample for the angle. */
+#include "aq_edge_dev.h"
+constexpr int kEdgeTileW = 64, kEdgeTileH = 16, kEdgeSrcW = kEdgeTileW + 6, kEdgeSrcH = kEdgeTileH + 6, kEdgeGaussW = kEdgeTileW + 2, kEdgeGaussH = kEdgeTileH + 2;
+__global__ __launch_bounds__(256) void k_aq_edge(const pixel* src, long stride, int width, int height, int blocksW, uint32_t* density, uint32_t* avgAngle,
+                                                  unsigned long long* part, pixel* edgePlane, pixel* thetaPlane)
+{
+    __shared__ uint16_t s[kEdgeSrcH][kEdgeSrcW + 2];
+    __shared__ uint16_t g[kEdgeGaussH][kEdgeGaussW + 2];
+    const int tid = threadIdx.x, x0 = blockIdx.x * kEdgeTileW, y0 = blockIdx.y * kEdgeTileH;
+    for (int i = tid; i < kEdgeSrcH * kEdgeSrcW; i += 256)
+    {
+        const int r = i / kEdgeSrcW, c = i - r * kEdgeSrcW, x = x0 - 3 + c, y = y0 - 3 + r;
+        s[r][c] = x >= 0 && y >= 0 && x < width && y < height ? (uint16_t)src[(long)y * stride + x] : (uint16_t)0;
+    }
+    __syncthreads();
+    for (int i = tid; i < kEdgeGaussH * kEdgeGaussW; i += 256)
+    {
+        const int r = i / kEdgeGaussW, c = i - r * kEdgeGaussW, x = x0 - 1 + c, y = y0 - 1 + r;
+        int v = s[r + 2][c + 2];
+        if (x >= 2 && y >= 2 && x < width - 2 && y < height - 2)
+        {
+            const int k[3] = { 2, 4, 5 }, m[3] = { 4, 9, 12 }, n[3] = { 5, 12, 15 };
+            int sum = 0;
+#pragma unroll
+            for (int dx = 0; dx < 5; dx++)
+            {
+                const int j = dx < 3 ? dx : 4 - dx;
+                sum += k[j] * (s[r][c + dx] + s[r + 4][c + dx]) + m[j] * (s[r + 1][c + dx] + s[r + 3][c + dx]) + n[j] * s[r + 2][c + dx];
+            }
+            v = sum / 159;
+        }
+        g[r][c] = (uint16_t)v;
+    }
+    __syncthreads();
+    const int wave = tid >> 6, lane = tid & 63, bx = blockIdx.x * (kEdgeTileW / 16) + wave;
+    if (bx >= blocksW) return;
+    uint32_t sum = 0, ssd = 0, angles = 0;
+#pragma unroll
+    for (int i = 0; i < 4; i++)
+    {
+        const int px = wave * 16 + (lane & 15), py = (lane >> 4) + 4 * i, x = x0 + px, y = y0 + py;
+        if (x >= width || y >= height) continue;
+        uint32_t e, t = 0;
+        if (x == 0 || y == 0 || x == width - 1 || y == height - 1)
+            e = s[py + 3][px + 3];
+        else
+        {
+            const int tl = g[py][px], tc = g[py][px + 1], tr = g[py][px + 2], ml = g[py + 1][px], mr = g[py + 1][px + 2], bl = g[py + 2][px], bc = g[py + 2][px + 1], br = g[py + 2][px + 2];
+            const int gh = -3 * tl + 3 * tr - 10 * ml + 10 * mr - 3 * bl + 3 * br;
+            const int gv = -3 * tl - 10 * tc - 3 * tr + 3 * bl + 10 * bc + 3 * br;
+            t = (uint32_t)xa_edge_theta(gv, gh);
+            e = xa_edge_is_edge(gv, gh, XA_PIXEL_MAX) ? XA_PIXEL_MAX : 0;
+        }
+        if (edgePlane) edgePlane[(long)y * width + x] = (pixel)e;
+        if (thetaPlane) thetaPlane[(long)y * width + x] = (pixel)t;
+        sum += e; ssd += e * e; angles += t;
+    }
+    sum = xa_wave_sum(sum); ssd = xa_wave_sum(ssd); angles = xa_wave_sum(angles);
+    if (lane == 0)
+    {
+        const size_t blk = (size_t)blockIdx.y * blocksW + bx;
+        density[blk] = ssd - (uint32_t)(((unsigned long long)sum * sum) >> 8);
+        avgAngle[blk] = angles >> 8;
+        part[blk * 2] = sum; part[blk * 2 + 1] = ssd;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_aq_edge_reduce(const unsigned long long* part, int numBlocks, unsigned long long* wpSum, unsigned long long* wpSsd)
+{
+    __shared__ unsigned long long t[256];
+    unsigned long long a = 0;
+    for (int i = threadIdx.x; i < numBlocks; i += 256) a += part[(size_t)i * 2 + blockIdx.x];
+    t[threadIdx.x] = a;
+    __syncthreads();
+    for (int k = 128; k > 0; k >>= 1) { if ((int)threadIdx.x < k) t[threadIdx.x] += t[threadIdx.x + k]; __syncthreads(); }
+    if (threadIdx.x == 0) *(blockIdx.x ? wpSsd : wpSum) += t[0];
+}
+
+/* x265amd_aq_edge with the two words to add to given one by one (the encoder's six words keep the luma sum at [0] and the luma sum of squares at [3]) */
+int xa_aq_edge(void* stream, uint64_t luma, intptr_t stride, int width, int height, int qg_size, uint32_t* d_density, uint32_t* d_avg_angle, uint64_t* d_wp_sum, uint64_t* d_wp_ssd,
+               uint64_t edge_plane, uint64_t theta_plane)
+{
+    if (!luma || !d_density || !d_avg_angle || !d_wp_sum || !d_wp_ssd || width <= 0 || height <= 0 || stride < width || qg_size != 16)
+        return xa_fail(X265AMD_EINVAL, "x265amd_aq_edge: bad arguments (quantisation groups of 16 only)");
+    const int bw = (width + 15) / 16, bh = (height + 15) / 16;
+    hipStream_t st = (hipStream_t)stream;
+    static thread_local void* dPart = nullptr; static thread_local size_t partBytes = 0;
+    const size_t need = (size_t)bw * bh * 2 * sizeof(unsigned long long);
+    if (need > partBytes)
+    {
+        if (dPart) { (void)hipStreamSynchronize(st); xa_scratch_free(dPart); dPart = nullptr; partBytes = 0; }
+        if (xa_scratch_alloc(&dPart, need) != hipSuccess) return xa_fail(X265AMD_EHIP, "x265amd_aq_edge: device allocation");
+        partBytes = need;
+    }
+    hipLaunchKernelGGL(k_aq_edge, dim3((bw + kEdgeTileW / 16 - 1) / (kEdgeTileW / 16), bh), dim3(256), 0, st, (const pixel*)(uintptr_t)luma, (long)stride, width, height, bw,
+                       d_density, d_avg_angle, (unsigned long long*)dPart, (pixel*)(uintptr_t)edge_plane, (pixel*)(uintptr_t)theta_plane);
+    hipLaunchKernelGGL(k_aq_edge_reduce, dim3(2), dim3(256), 0, st, (const unsigned long long*)dPart, bw * bh, (unsigned long long*)d_wp_sum, (unsigned long long*)d_wp_ssd);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return xa_fail(X265AMD_EHIP, hipGetErrorString(e));
+    return X265AMD_OK;
+}
+extern "C" int x265amd_aq_edge(void* stream, uint64_t luma, intptr_t stride, int width, int height, int qg_size, uint32_t* d_density, uint32_t* d_avg_angle, uint64_t* d_wp,
+                               uint64_t edge_plane, uint64_t theta_plane)
+{
+    if (!d_wp) return xa_fail(X265AMD_EINVAL, "x265amd_aq_edge: bad arguments (quantisation groups of 16 only)");
+    return xa_aq_edge(stream, luma, stride, width, height, qg_size, d_density, d_avg_angle, d_wp, d_wp + 1, edge_plane, theta_plane);
+}
+
+/* the per-sample arithmetic of k_aq_edge on given gradient pairs: what the device makes of aq_edge_dev.h, to be held against the host's copy (x265amd_aq_edge_angles) */
+__global__ __launch_bounds__(256) void k_aq_edge_angles(const int32_t* gv, const int32_t* gh, int count, int32_t* theta, int32_t* edge)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= count) return;
+    theta[i] = xa_edge_theta(gv[i], gh[i]);
+    edge[i] = xa_edge_is_edge(gv[i], gh[i], XA_PIXEL_MAX) ? XA_PIXEL_MAX : 0;
+}
+extern "C" int x265amd_aq_edge_angles_device(void* stream, const int32_t* d_gv, const int32_t* d_gh, int count, int32_t* d_theta, int32_t* d_edge)
+{
+    if (!d_gv || !d_gh || !d_theta || !d_edge || count <= 0) return xa_fail(X265AMD_EINVAL, "x265amd_aq_edge_angles_device: bad arguments");
+    hipLaunchKernelGGL(k_aq_edge_angles, dim3((count + 255) / 256), dim3(256), 0, (hipStream_t)stream, d_gv, d_gh, count, d_theta, d_edge);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return xa_fail(X265AMD_EHIP, hipGetErrorString(e));
+    return X265AMD_OK;
+}

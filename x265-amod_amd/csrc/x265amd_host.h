@@ -33,6 +33,10 @@ void xa_scratch_local_end();
  * (measured, dbg/README.md).  Kernel boundaries hid that; keeping the directions apart removes it. */
 hipError_t xa_mapped_alloc(void** p, size_t bytes, bool deviceWrites = false);
 void xa_mapped_free(void* p);
+
+/* x265amd_aq_edge (lowres_kernels.hip) with the picture's two sums named one by one: the encoder keeps the luma sum and the luma sum of squares three words apart */
+int xa_aq_edge(void* stream, uint64_t luma, intptr_t stride, int width, int height, int qg_size, uint32_t* d_density, uint32_t* d_avg_angle, uint64_t* d_wp_sum, uint64_t* d_wp_ssd,
+               uint64_t edge_plane, uint64_t theta_plane);
 #ifdef __cplusplus
 struct XaMapped
 {

@@ -1,9 +1,11 @@
 /* Adaptive quantisation, the host half (include/x265amd.h: x265amd_aq_offsets): LookaheadTLD::calcAdaptiveQuantFrame (reference:
  * source/encoder/slicetype.cpp:452-640) from the block energies of x265amd_aq_energy to the per-block QP offsets, for --aq-mode 1 (variance),
- * 2 (auto-variance) and 3 (auto-variance with a bias to dark scenes); no HDR10 luma offsets, external quant offsets, hevc-aq or edge modes.
+ * 2 (auto-variance) and 3 (auto-variance with a bias to dark scenes), and x265amd_aq_offsets_edge for 4 (edge) and 5 (edge with a bias to dark scenes); no HDR10
+ * luma offsets, external quant offsets or hevc-aq.
  * Double-precision arithmetic in the reference's order and operand types (float constants widen exactly where they do there), so that the
  * offsets -- which feed rounding to integer QPs and the fixed-point factors below -- come out bit for bit. */
 #include "x265amd.h"
+#include "../csrc/aq_edge_dev.h"
 #include <math.h>
 
 namespace {
@@ -72,6 +74,61 @@ extern "C" int x265amd_aq_offsets(const uint32_t* energy, int numBlocks, int blo
         qpAqOffset[b] = offset;
         qpCuTreeOffset[b] = offset;
         invQscaleFactor[b] = exp2fix8(offset);
+    }
+    return X265AMD_OK;
+}
+
+/* --aq-mode 4 (X265_AQ_EDGE) and 5 (X265_AQ_EDGE_BIASED): slicetype.cpp:537-577 (first pass) and :596-615 (second pass); density / avgAngle: edgeDensityCu's */
+extern "C" int x265amd_aq_offsets_edge(const uint32_t* energy, const uint32_t* density, const uint32_t* avgAngle, int numBlocks, int blockCount, int aqMode, double aqStrength,
+                                       double aqBiasStrength, int qgSize, double* qpAqOffset, double* qpCuTreeOffset, int32_t* invQscaleFactor)
+{
+    if (!energy || !density || !avgAngle || !qpAqOffset || !qpCuTreeOffset || !invQscaleFactor || blockCount <= 0 || numBlocks <= 0 || (aqMode != 4 && aqMode != 5) || qgSize != 16 || aqStrength == 0)
+        return X265AMD_EINVAL;
+    const float autoBase = 11.f;
+    const int inclination = 45;                     /* EDGE_INCLINATION (slicetype.h:44) */
+    double meanSquare = 0, meanRoot = 0, offset = 0;
+    const double toEightBit = 1.f / (1 << (2 * (X265AMD_DEPTH - 8)));
+    for (int b = 0; b < numBlocks; b++)
+    {
+        offset = pow((density[b] ? density[b] : energy[b]) * toEightBit + 1, 0.1);
+        qpCuTreeOffset[b] = offset;
+        meanRoot += offset;
+        meanSquare += offset * offset;
+    }
+    meanRoot /= blockCount;
+    meanSquare /= blockCount;
+    const double strength = aqStrength * meanRoot;
+    meanRoot = meanRoot - 0.5f * (meanSquare - autoBase) / meanRoot;
+    const double darkBias = aqBiasStrength * aqStrength;
+    for (int b = 0; b < numBlocks; b++)
+    {
+        const uint32_t a = avgAngle[b];
+        /* Lowres::edgeInclined: the block's edges run near a multiple of 45 degrees */
+        const bool inclined = density[b] && ((a >= (uint32_t)(inclination - 15) && a <= (uint32_t)(inclination + 15)) || (a >= (uint32_t)(inclination + 75) && a <= (uint32_t)(inclination + 105)));
+        offset = qpCuTreeOffset[b];
+        const double bias = darkBias * (1.f - autoBase / (offset * offset)) / 10.f;
+        if (inclined && (offset - meanRoot > 0))
+            offset = (strength + 0.5) * (offset - meanRoot);           /* AQ_EDGE_BIAS (slicetype.h:43) */
+        else
+            offset = strength * (offset - meanRoot);
+        if (aqMode == 5) offset += bias;
+        qpAqOffset[b] = offset;
+        qpCuTreeOffset[b] = offset;
+        invQscaleFactor[b] = exp2fix8(offset);
+    }
+    return X265AMD_OK;
+}
+
+/* the angle and the edge decision of x265amd_aq_edge's samples, computed by the host from the same source text (csrc/aq_edge_dev.h); |gradient| < 2^15 */
+extern "C" int x265amd_aq_edge_angles(const int32_t* gv, const int32_t* gh, int count, int32_t* theta, int32_t* edge)
+{
+    if (!gv || !gh || !theta || !edge || count <= 0) return X265AMD_EINVAL;
+    const int white = (1 << X265AMD_DEPTH) - 1;
+    for (int i = 0; i < count; i++)
+    {
+        if (gv[i] <= -32768 || gv[i] >= 32768 || gh[i] <= -32768 || gh[i] >= 32768) return X265AMD_EINVAL;
+        theta[i] = xa_edge_theta(gv[i], gh[i]);
+        edge[i] = xa_edge_is_edge(gv[i], gh[i], white) ? white : 0;
     }
     return X265AMD_OK;
 }

@@ -922,7 +922,8 @@ int x265amd_check_intra(void* stream, const x265amd_slice_info* si, const x265am
  * (:3145-3277), topSkipMinDepth (:3428-3476), recursionDepthCheck (:3479-3534), addSplitFlagCost (:3405-3426).  Host recursion in the
  * reference's order over the batch entry points above; one CTU per call.
  * Built subset: rd levels 2-6; I, P and B slices (b_intra 0 / 1), 2Nx2N / rect / amp partitions, limit_refs 0-3, limit_modes 0 / 1, no delta QP,
- * rd_level 3-4, rskip 0 / 1, early_skip 0 / 1.  Anything else is rejected with X265AMD_EINVAL. */
+ * rd_level 3-4, rskip 0 / 1 (2, the edge-based form, through the _ex entries further down, which take the picture's edge counts), early_skip 0 / 1.  Anything
+ * else is rejected with X265AMD_EINVAL. */
 typedef struct x265amd_analysis_params
 {
     double psy_rd;                  /* param.psyRd */
@@ -1162,6 +1163,31 @@ int x265amd_aq_offsets_edge(const uint32_t* energy, const uint32_t* density, con
  * the host's against the reference's arithmetic over every pair (tests/native/aq_theta_check.cpp). */
 int x265amd_aq_edge_angles(const int32_t* gv, const int32_t* gh, int count, int32_t* theta, int32_t* edge);
 int x265amd_aq_edge_angles_device(void* stream, const int32_t* d_gv, const int32_t* d_gh, int count, int32_t* d_theta, int32_t* d_edge);
+
+/* The edge-based recursion skip (--rskip 2: EDGE_BASED_RSKIP).
+ * x265amd_rskip_edge_counts = computeEdge on a SOURCE picture with no angle plane and white pixel 1 (reference: source/encoder/frameencoder.cpp:474-484,
+ * source/encoder/slicetype.cpp:98-157), counted: the bit plane is 1 where the 3x3 Sobel (weights 3 / 10 / 3) of the luma samples has gH * gH + gV * gV >= T * T
+ * (T the largest sample value), 0 elsewhere and on the picture's outermost row and column.  d_counts[by * ceil(width / 32) + bx] = the number of ones inside the
+ * 32x32 block (bx, by); samples beyond width x height count as 0.  luma: device address of sample (0,0); only samples inside width x height are read.
+ * Asynchronous.  x265amd_rskip_edge_model: the same plane and counts in host code (plane: NULL, or width x height bytes; counts: NULL, or the blocks). */
+int x265amd_rskip_edge_counts(void* stream, uint64_t luma, intptr_t stride, int width, int height, uint32_t* d_counts);
+int x265amd_rskip_edge_model(const x265amd_pixel* luma, intptr_t stride, int width, int height, uint8_t* plane, uint32_t* counts);
+/* Analysis::complexityCheckCU's edge branch (reference: source/encoder/analysis.cpp:3561-3577) for a CU of cu_size x cu_size samples (64 or 32) that holds `count`
+ * ones: 1 = the recursion ends here (the plane's variance over the CU is not above the threshold), 0 = go on.  threshold: param.edgeVarThreshold, a float. */
+int x265amd_rskip_edge_skip(uint32_t count, int cu_size, float threshold);
+/* x265amd_compress_ctu_inter / x265amd_analyse_frame with the picture's edge counts: what ap->rskip == 2 needs (without them the two entries above reject it).
+ * counts: HOST array, x265amd_rskip_edge_counts' result for the picture's source plane at the coded size; blocks_w: blocks per row, ceil(width / 32). */
+typedef struct x265amd_rskip_edge { const uint32_t* counts; int32_t blocks_w; float threshold; } x265amd_rskip_edge;
+int x265amd_compress_ctu_inter_ex(x265amd_me_ctx* me, void* stream, const x265amd_mvpred_info* info, const x265amd_inter_search_params* sp,
+                                  const x265amd_slice_info* si, const x265amd_analysis_params* ap, x265amd_cu_unit* units, x265amd_mv_unit* cur,
+                                  const x265amd_mv_unit* col, const uint8_t* ref_depth, const int8_t* ref_qp0, const uint64_t* h_planes, int num_pics,
+                                  intptr_t stride, intptr_t cstride, x265amd_cu_stat* cu_stat, int ctu_addr, const uint8_t* ctx_in, uint64_t frac_in,
+                                  int16_t* coeff_out, x265amd_ctu_result* out, const x265amd_rskip_edge* edge);
+int x265amd_analyse_frame_ex(x265amd_me_ctx* me, void* stream, const x265amd_mvpred_info* info, const x265amd_inter_search_params* sp,
+                             const x265amd_slice_info* si, const x265amd_analysis_params* ap, x265amd_cu_unit* units, x265amd_mv_unit* cur,
+                             const x265amd_mv_unit* col, const uint8_t* ref_depth, const int8_t* ref_qp0, const uint64_t* h_planes, int num_pics,
+                             intptr_t stride, intptr_t cstride, x265amd_cu_stat* cu_stat, int16_t* coeff_out, x265amd_ctu_result* results,
+                             uint8_t* slice_data, size_t cap, uint32_t* substream_sizes, int* num_substreams, const x265amd_rskip_edge* edge);
 
 /* returns the device scratch the host orchestrators keep between calls (a size-class pool) to the HIP runtime */
 void x265amd_release_scratch(void);

@@ -32,7 +32,9 @@ typedef struct x265amd_param
     double ipFactor, pbFactor;              /* rc.ipFactor / rc.pbFactor: QP offsets of I and B slices */
     int32_t rdLevel;                        /* 2..6 */
     int32_t bEnableRectInter, bEnableAMP, limitModes, limitReferences;
-    int32_t bEnableEarlySkip, recursionSkipMode, bIntraInBFrames;
+    int32_t bEnableEarlySkip, recursionSkipMode, bIntraInBFrames;       /* recursionSkipMode (--rskip): 0 off, 1 the RD-cost form, 2 the edge-based form (EDGE_BASED_RSKIP:
+                                                                         * an edge bit plane of every P / B picture's source, x265amd_rskip_edge_counts; edgeVarThreshold at the
+                                                                         * end of the struct; not with aqMode 4 / 5, not with shardCount > 1) */
     double psyRd;
     int32_t searchMethod, subpelRefine, searchRange;       /* X265AMD_ME_* (dia / hex / star / full), subme, merange */
     int32_t maxNumMergeCand;
@@ -139,7 +141,8 @@ typedef struct x265amd_param
     int32_t deblockingFilterTCOffset, deblockingFilterBetaOffset;      /* param.deblockingFilter*Offset (--deblock tc:beta, each -6 .. 6): pps_tc_offset_div2 / pps_beta_offset_div2 */
     int32_t limitTU;                        /* param.limitTU (--limit-tu; --preset slower has 4): 0, 2 (depth first), 3 (neighbourhood), 4 (both); 1 (breadth first) is not built.
                                              * Needs tuQTMaxInterDepth > 1 (else it is switched off, encoder.cpp:4103-4107) */
-    int32_t reserved5;
+    float edgeVarThreshold;                 /* param.edgeVarThreshold (--rskip-edge-threshold N stores (float)N * 0.01f as the reference's build does; default 0.05f): read only under recursionSkipMode 2, within 0 .. 1.
+                                             * (The slot was a reserved int32 until the edge-based recursion skip was built: same offset, same four bytes) */
 } x265amd_param;
 enum { X265AMD_RC_CQP = 1, X265AMD_RC_CRF = 2 };
 

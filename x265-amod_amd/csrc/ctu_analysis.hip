@@ -16,7 +16,7 @@
  * I slices take compressIntraCU (:514-668): checkIntra 2Nx2N (+ NxN at 8x8) through x265amd_check_intra, then the four sub-CUs.
  *
  * Scope of this entry point: I, P and B slices (intra candidates through x265amd_intra_in_inter; --b-intra on / off), 2Nx2N, rectangular
- * (--rect) and asymmetric (--amp) partitions with --limit-modes, --limit-refs 0-3, no delta QP (aq-mode 0, no cutree), rd 3-4, rskip 0/1, early skip on/off.
+ * (--rect) and asymmetric (--amp) partitions with --limit-modes, --limit-refs 0-3, no delta QP (aq-mode 0, no cutree), rd 3-4, rskip 0/1 (2 with the picture's edge counts), early skip on/off.
  */
 #include "x265amd_dev.h"
 #include "inter_common.h"
@@ -243,6 +243,16 @@ struct Analyzer
      * last sub-CU's value), and the per-CTU records it is loaded from (CUData::m_refTuDepth[geomRecurId]: the deepest transform unit of the CU decided at that place) */
     int maxTUDepth = -1;
     const XaTuRecs* tuRecs = nullptr;
+    const x265amd_rskip_edge* edge = nullptr;       /* rskip 2: the picture's edge counts per 32x32 block and the threshold */
+    /* Analysis::complexityCheckCU, the edge branch (analysis.cpp:3561-3577), for a 64x64 or 32x32 CU that lies inside the picture */
+    bool edgeSkipsRecursion(int x, int y, int size) const
+    {
+        const int bx = x >> 5, by = y >> 5, n = size >> 5;
+        uint32_t count = 0;
+        for (int j = 0; j < n; j++)
+            for (int i = 0; i < n; i++) count += edge->counts[(size_t)(by + j) * edge->blocks_w + bx + i];
+        return x265amd_rskip_edge_skip(count, size, edge->threshold) != 0;
+    }
     static int geomId(int lx, int ly, int depth) { return depth == 0 ? 0 : depth == 1 ? 1 + (ly >> 5) * 2 + (lx >> 5) : 5 + (ly >> 4) * 4 + (lx >> 4); }        /* calcCTUGeoms: raster inside a depth */
     /* Analysis::loadTUDepth (analysis.cpp:375-424) */
     void loadTUDepth(int x, int y, int depth)
@@ -1561,7 +1571,7 @@ struct Analyzer
         return 0;
     }
 
-    /* compressInterCU_rd5_6 (analysis.cpp:1850-2417) without analysis reuse / CTU info / lossless / edge-based rskip */
+    /* compressInterCU_rd5_6 (analysis.cpp:1850-2417) without analysis reuse / CTU info / lossless */
     int compress56(int x, int y, int depth, SplitData& splitOut)
     {
         ModeDepth& d = md[depth];
@@ -1593,6 +1603,7 @@ struct Analyzer
             skipModes = A->early_skip && d.best && !rootCbf(*d.best);
             if (interRd(0, PRED_2Nx2N, allSplitRefs, 0)) return err;
             if (A->rskip == 1 && depth && md[depth - 1].best) skipRecursion = d.best && !rootCbf(*d.best);
+            else if (A->rskip == 2 && log2 >= 5) skipRecursion = d.best && edgeSkipsRecursion(x, y, size);          /* analysis.cpp:2028-2029 */
         }
         /* Step 2: the four sub-blocks in series */
         if (mightSplit && !skipRecursion)
@@ -2049,6 +2060,8 @@ struct Analyzer
                 if (I->pic_height >= 1080 && !skipRecursion && A->rd_level == 2 && size != 64)
                     skipRecursion = (double)d.srcHomo < (.1 * d.srcMean);
             }
+            /* the edge-based form (analysis.cpp:1329-1332): 64x64 and 32x32 CUs, whatever minDepth says */
+            else if (mightSplit && !skipRecursion && A->rskip == 2 && log2 >= 5) skipRecursion = edgeSkipsRecursion(x, y, size);
         }
         /* the intra try of step 3 depends on nothing that happens until then: when the CU is not skipped and a queue is to spare it starts now, beside the sub-CUs
          * and the motion searches (intra_rd.hip; a try the analysis does not get to is dropped) */
@@ -2285,7 +2298,8 @@ static int compress_ctu_impl(x265amd_me_ctx* me, void* stream, const x265amd_mvp
                              const x265amd_slice_info* si, const x265amd_analysis_params* A, x265amd_cu_unit* units, x265amd_mv_unit* cur,
                              const x265amd_mv_unit* col, const uint8_t* ref_depth, const int8_t* ref_qp0, const uint64_t* h_planes, int num_pics,
                              intptr_t stride, intptr_t cstride, x265amd_cu_stat* cu_stat, int ctu_addr, const uint8_t* ctx_in, uint64_t frac_in,
-                             int16_t* coeff_out, x265amd_ctu_result* out, XaMapUnit* dCur, const XaMapUnit* dCol, const int8_t* cu_qp = nullptr, const XaTuRecs* tu_recs = nullptr);
+                             int16_t* coeff_out, x265amd_ctu_result* out, XaMapUnit* dCur, const XaMapUnit* dCol, const int8_t* cu_qp = nullptr, const XaTuRecs* tu_recs = nullptr,
+                             const x265amd_rskip_edge* edge = nullptr);
 extern "C" int x265amd_compress_ctu_inter(x265amd_me_ctx* me, void* stream, const x265amd_mvpred_info* I, const x265amd_inter_search_params* S,
                                           const x265amd_slice_info* si, const x265amd_analysis_params* A, x265amd_cu_unit* units, x265amd_mv_unit* cur,
                                           const x265amd_mv_unit* col, const uint8_t* ref_depth, const int8_t* ref_qp0, const uint64_t* h_planes, int num_pics,
@@ -2295,11 +2309,20 @@ extern "C" int x265amd_compress_ctu_inter(x265amd_me_ctx* me, void* stream, cons
     return compress_ctu_impl(me, stream, I, S, si, A, units, cur, col, ref_depth, ref_qp0, h_planes, num_pics, stride, cstride, cu_stat, ctu_addr, ctx_in, frac_in, coeff_out, out,
                              (XaMapUnit*)xa_devmap_find(cur), (const XaMapUnit*)xa_devmap_find(col));
 }
+extern "C" int x265amd_compress_ctu_inter_ex(x265amd_me_ctx* me, void* stream, const x265amd_mvpred_info* I, const x265amd_inter_search_params* S,
+                                             const x265amd_slice_info* si, const x265amd_analysis_params* A, x265amd_cu_unit* units, x265amd_mv_unit* cur,
+                                             const x265amd_mv_unit* col, const uint8_t* ref_depth, const int8_t* ref_qp0, const uint64_t* h_planes, int num_pics,
+                                             intptr_t stride, intptr_t cstride, x265amd_cu_stat* cu_stat, int ctu_addr, const uint8_t* ctx_in, uint64_t frac_in,
+                                             int16_t* coeff_out, x265amd_ctu_result* out, const x265amd_rskip_edge* edge)
+{
+    return compress_ctu_impl(me, stream, I, S, si, A, units, cur, col, ref_depth, ref_qp0, h_planes, num_pics, stride, cstride, cu_stat, ctu_addr, ctx_in, frac_in, coeff_out, out,
+                             (XaMapUnit*)xa_devmap_find(cur), (const XaMapUnit*)xa_devmap_find(col), nullptr, nullptr, edge);
+}
 static int compress_ctu_impl(x265amd_me_ctx* me, void* stream, const x265amd_mvpred_info* I, const x265amd_inter_search_params* S,
                              const x265amd_slice_info* si, const x265amd_analysis_params* A, x265amd_cu_unit* units, x265amd_mv_unit* cur,
                              const x265amd_mv_unit* col, const uint8_t* ref_depth, const int8_t* ref_qp0, const uint64_t* h_planes, int num_pics,
                              intptr_t stride, intptr_t cstride, x265amd_cu_stat* cu_stat, int ctu_addr, const uint8_t* ctx_in, uint64_t frac_in,
-                             int16_t* coeff_out, x265amd_ctu_result* out, XaMapUnit* dCur, const XaMapUnit* dCol, const int8_t* cu_qp, const XaTuRecs* tu_recs)
+                             int16_t* coeff_out, x265amd_ctu_result* out, XaMapUnit* dCur, const XaMapUnit* dCol, const int8_t* cu_qp, const XaTuRecs* tu_recs, const x265amd_rskip_edge* edge)
 {
     if ((!me && si && si->slice_type != 2) || !I || !S || !si || !A || !units || !cur || !ref_depth || !ref_qp0 || !h_planes || !cu_stat || !ctx_in || !out || num_pics < 2)
         return xa_fail(X265AMD_EINVAL, "compress_ctu_inter: null argument");
@@ -2307,8 +2330,10 @@ static int compress_ctu_impl(x265amd_me_ctx* me, void* stream, const x265amd_mvp
     if (A->limit_tu < 0 || A->limit_tu > 4 || A->limit_tu == 1) return xa_fail(X265AMD_EINVAL, "compress_ctu_inter: limit_tu 1 (the breadth-first form) is not built");
     if (A->limit_tu >= 3 && (!tu_recs || !tu_recs->cur || (si->slice_type != 2 && !tu_recs->ref[0]) || (si->slice_type == 0 && !tu_recs->ref[1])))
         return xa_fail(X265AMD_EINVAL, "compress_ctu_inter: limit_tu 3 / 4 needs the pictures' transform depth records (the encoder object keeps them)");
-    if (A->rdoq_level < 0 || A->rdoq_level > 2 || A->rd_level < 2 || A->rd_level > 6 || (A->rd_level > 4 && A->rskip == 2) || A->limit_refs < 0 || A->limit_refs > 3 || (si->use_dqp && (!cu_qp || si->max_cu_dqp_depth < 0 || si->max_cu_dqp_depth > 1)) || si->tq_bypass_enabled || (A->rskip != 0 && A->rskip != 1))
-        return xa_fail(X265AMD_EINVAL, "compress_ctu_inter: configuration outside the built subset (rd 2-6, delta QP with the quantisation groups' QPs handed in and groups of 64 or 32 samples, rskip 0/1)");
+    if (A->rdoq_level < 0 || A->rdoq_level > 2 || A->rd_level < 2 || A->rd_level > 6 || A->limit_refs < 0 || A->limit_refs > 3 || (si->use_dqp && (!cu_qp || si->max_cu_dqp_depth < 0 || si->max_cu_dqp_depth > 1)) || si->tq_bypass_enabled || (A->rskip != 0 && A->rskip != 1 && !(A->rskip == 2 && edge)))
+        return xa_fail(X265AMD_EINVAL, "compress_ctu_inter: configuration outside the built subset (rd 2-6, delta QP with the quantisation groups' QPs handed in and groups of 64 or 32 samples, rskip 0/1, rskip 2 with the picture's edge counts)");
+    /* (an I slice never asks: its record may come without counts) */
+    if (A->rskip == 2 && si->slice_type != 2 && (!edge->counts || edge->blocks_w < (si->pic_width + 31) / 32)) return xa_fail(X265AMD_EINVAL, "compress_ctu_inter: rskip 2 needs the edge counts of the whole picture");
     if ((I->pic_width & 7) || (I->pic_height & 7) || I->pic_width != si->pic_width || I->pic_height != si->pic_height) return xa_fail(X265AMD_EINVAL, "compress_ctu_inter: picture size");
     /* debugging aid: X265AMD_DUMP_CTU=<dir> X265AMD_DUMP_POC=<poc> X265AMD_DUMP_MARGIN=<mx>,<my> writes every input of this call (before) and its outputs
      * (after) to <dir>/ctu_<addr>.bin so that the reference's compressCTU can be run on exactly the same state (dbg/ctu_replay.py) */
@@ -2351,7 +2376,7 @@ static int compress_ctu_impl(x265amd_me_ctx* me, void* stream, const x265amd_mvp
     Analyzer& a = *an;
     XA_HOSTPROF("ctu.all but new / delete");
     a.me = me; a.st = (hipStream_t)stream; a.I = I; a.S = S; a.si = si; a.A = A; a.units = units; a.cur = cur; a.col = col;
-    a.tuRecs = tu_recs;
+    a.tuRecs = tu_recs; a.edge = edge;
     if (tu_recs && tu_recs->cur) memset(tu_recs->cur + (size_t)ctu_addr * 21, -1, 21);          /* CUData::initCTU (cudata.cpp:312-313) */
     a.refDepth = ref_depth; a.refQp0 = ref_qp0; a.planes = h_planes; a.numPics = num_pics; a.stride = stride; a.cstride = cstride;
     a.cuStat = cu_stat; a.ctuAddr = ctu_addr; a.ctuW = (I->pic_width + 63) >> 6; a.w4 = I->pic_width >> 2; a.h4 = I->pic_height >> 2;
@@ -2446,6 +2471,15 @@ extern "C" int x265amd_analyse_frame(x265amd_me_ctx* me, void* stream, const x26
     return xa_analyse_frame(me, stream, I, S, si, A, units, cur, col, ref_depth, ref_qp0, h_planes, num_pics, stride, cstride, cu_stat, coeff_out, results, slice_data, cap,
                             substream_sizes, num_substreams, nullptr);
 }
+extern "C" int x265amd_analyse_frame_ex(x265amd_me_ctx* me, void* stream, const x265amd_mvpred_info* I, const x265amd_inter_search_params* S,
+                                        const x265amd_slice_info* si, const x265amd_analysis_params* A, x265amd_cu_unit* units, x265amd_mv_unit* cur,
+                                        const x265amd_mv_unit* col, const uint8_t* ref_depth, const int8_t* ref_qp0, const uint64_t* h_planes, int num_pics,
+                                        intptr_t stride, intptr_t cstride, x265amd_cu_stat* cu_stat, int16_t* coeff_out, x265amd_ctu_result* results,
+                                        uint8_t* slice_data, size_t cap, uint32_t* substream_sizes, int* num_substreams, const x265amd_rskip_edge* edge)
+{
+    return xa_analyse_frame(me, stream, I, S, si, A, units, cur, col, ref_depth, ref_qp0, h_planes, num_pics, stride, cstride, cu_stat, coeff_out, results, slice_data, cap,
+                            substream_sizes, num_substreams, nullptr, nullptr, nullptr, edge);
+}
 
 /* hooks (pictures coded in parallel, FrameEncoder::compressFrame's row loop, frameencoder.cpp:880-960): before_row blocks until the reference pictures have
  * finished the rows this CTU row may read; after_row hands the analysed row to the in-loop filters */
@@ -2453,7 +2487,7 @@ int xa_analyse_frame(x265amd_me_ctx* me, void* stream, const x265amd_mvpred_info
                      const x265amd_slice_info* si, const x265amd_analysis_params* A, x265amd_cu_unit* units, x265amd_mv_unit* cur,
                      const x265amd_mv_unit* col, const uint8_t* ref_depth, const int8_t* ref_qp0, const uint64_t* h_planes, int num_pics,
                      intptr_t stride, intptr_t cstride, x265amd_cu_stat* cu_stat, int16_t* coeff_out, x265amd_ctu_result* results,
-                     uint8_t* slice_data, size_t cap, uint32_t* substream_sizes, int* num_substreams, const XaRowHooks* hooks, const int8_t* cu_qp, const XaTuRecs* tu_recs)
+                     uint8_t* slice_data, size_t cap, uint32_t* substream_sizes, int* num_substreams, const XaRowHooks* hooks, const int8_t* cu_qp, const XaTuRecs* tu_recs, const x265amd_rskip_edge* edge)
 {
     if (!I || !si || !units || !cur || !cu_stat || !coeff_out) return xa_fail(X265AMD_EINVAL, "analyse_frame: null argument");
     const int ctuW = (si->pic_width + 63) >> 6, ctuH = (si->pic_height + 63) >> 6, numCtu = ctuW * ctuH, w4 = si->pic_width >> 2, h4 = si->pic_height >> 2;
@@ -2500,7 +2534,7 @@ int xa_analyse_frame(x265amd_me_ctx* me, void* stream, const x265amd_mvpred_info
         x265amd_ctu_result res;
         int16_t* coeff = coeff_out + (size_t)addr * kTileElems;
         int r = compress_ctu_impl(me, st, I, S, si, A, units, cur, col, ref_depth, ref_qp0, h_planes, num_pics, stride, cstride, cu_stat, addr,
-                                  rowCoder->ctx, A->use_sao ? rowCoder->fracBits : 0, coeff, &res, frameDCur, frameDCol, cu_qp, tu_recs);
+                                  rowCoder->ctx, A->use_sao ? rowCoder->fracBits : 0, coeff, &res, frameDCur, frameDCol, cu_qp, tu_recs, edge);
         if (r != X265AMD_OK) return r;
         if (results) results[addr] = res;
         xa_phase(XA_PH_ANALYZER);

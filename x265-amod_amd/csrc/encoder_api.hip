@@ -18,7 +18,7 @@ extern "C" void x265amd_param_default(x265amd_param* p)
     p->fpsNum = 25; p->fpsDenom = 1;
     p->bframes = 0; p->keyframeMax = 250; p->maxNumReferences = 3; p->qp = 30; p->ipFactor = 1.4f; p->pbFactor = 1.3f;      /* (float literals, as common/param.cpp:276-277 has them) */
     p->rateControlMode = X265AMD_RC_CQP; p->rfConstant = 28; p->aqStrength = 1.0; p->qCompress = 0.6; p->aqMode = 0; p->cuTree = 0; p->qgSize = 32; p->qpMin = 0; p->qpMax = 69; p->vuiVideoFormat = 5; p->vuiColorPrimaries = 2; p->vuiTransfer = 2; p->vuiMatrix = 2; p->bEmitCLL = 1;
-    p->rdLevel = 3; p->limitReferences = 3; p->bEnableEarlySkip = 1; p->recursionSkipMode = 1; p->bIntraInBFrames = 1; p->psyRd = 2.0;
+    p->rdLevel = 3; p->limitReferences = 3; p->bEnableEarlySkip = 1; p->recursionSkipMode = 1; p->bIntraInBFrames = 1; p->psyRd = 2.0; p->edgeVarThreshold = 0.05f;         /* (common/param.cpp:216) */
     p->searchMethod = X265AMD_ME_HEX; p->subpelRefine = 2; p->searchRange = 57; p->maxNumMergeCand = 3;
     p->bEnableSignHiding = 1; p->bEnableStrongIntraSmoothing = 1; p->bEnableTemporalMvp = 1; p->tuQTMaxInterDepth = 1; p->tuQTMaxIntraDepth = 1;
     p->bEnableLoopFilter = 1; p->bEnableSAO = 1; p->bEnableWavefront = 1; p->aspectRatioIdc = 0;
@@ -141,7 +141,11 @@ extern "C" x265amd_encoder* x265amd_encoder_open(const x265amd_param* p)
         XA_REQUIRE(p->subpelRefine >= 0 && p->subpelRefine <= 7, "subpelRefine outside 0..7");
         XA_REQUIRE(p->rdoqLevel >= 0 && p->rdoqLevel <= 2, "rdoqLevel outside 0..2");
         XA_REQUIRE(p->psyRdoqFix8 >= 0, "psyRdoqFix8 negative");
-        XA_REQUIRE(p->recursionSkipMode >= 0 && p->recursionSkipMode <= 1, "recursionSkipMode: only 0 and 1 are built (no edge-based rskip)");
+        XA_REQUIRE(p->recursionSkipMode >= 0 && p->recursionSkipMode <= 2, "recursionSkipMode outside 0..2");
+        /* the edge-based form: under aq-mode 4 / 5 (as they stand after the rules above) the reference takes its bit plane from the Gaussian-filtered edge picture, which is not built */
+        XA_REQUIRE(p->recursionSkipMode != 2 || p->aqMode < 4, "recursionSkipMode 2 with aqMode 4 / 5 is not built (the bit plane would come from the filtered edge picture)");
+        XA_REQUIRE(p->recursionSkipMode != 2 || (p->edgeVarThreshold >= 0.0f && p->edgeVarThreshold <= 1.0f), "edgeVarThreshold outside 0..1 (--rskip-edge-threshold 0..100)");
+        XA_REQUIRE(p->recursionSkipMode != 2 || p->shardCount <= 1, "recursionSkipMode 2 with pictures coded on several GPUs (shardCount > 1) is not built");
         XA_REQUIRE(p->limitReferences >= 0 && p->limitReferences <= 3, "limitReferences outside 0..3");
         XA_REQUIRE(!p->bEnableAMP || p->bEnableRectInter, "bEnableAMP needs bEnableRectInter");
 #undef XA_REQUIRE

@@ -143,6 +143,21 @@ static int sliceNal(const x265amd_encoder& e, Pic& pic, const FrameCtx& c, const
     return 0;
 }
 
+/* --rskip 2, before the CTU loop of a P / B picture (FrameEncoder::compressFrame, frameencoder.cpp:474-484: computeEdge on the source picture at the coded size, padding
+ * included): one launch of the device pass on the picture's stream, its counts written into mapped host memory kept with the picture, one wait.  What every CTU row of the
+ * picture reads afterwards -- under WPP and with pictures coded in parallel alike -- is that one array. */
+int x265amd_encoder::edgeCounts(Pic& pic, hipStream_t st, x265amd_rskip_edge& edge)
+{
+    const int bw = (W + 31) / 32, bh = (H + 31) / 32;
+    if (!pic.dSrc) return xa_fail(X265AMD_EINVAL, "encoder: the picture's source is gone");
+    if (!pic.edgeCounts && xa_mapped_alloc((void**)&pic.edgeCounts, (size_t)bw * bh * sizeof(uint32_t), true) != hipSuccess) return xa_fail(X265AMD_EHIP, "encoder: edge counts");
+    const int rc = x265amd_rskip_edge_counts(st, planeAddr(pic.dSrc, 0), stride, W, H, pic.edgeCounts);
+    if (rc != X265AMD_OK) return rc;
+    if (hipStreamSynchronize(st) != hipSuccess) return xa_fail(X265AMD_EHIP, "encoder: edge counts");
+    edge.counts = pic.edgeCounts; edge.blocks_w = bw; edge.threshold = p.edgeVarThreshold;
+    return X265AMD_OK;
+}
+
 /* FrameEncoder::compressFrame for one picture (its own thread and HIP stream).  The analysis starts when every reference picture is final; the
  * in-loop filters, SAO (its decision carries state from picture to picture, SAO::m_depthSaoRate) and the shared filter scratch run in coding
  * order, i.e. after the previous picture's task. */
@@ -198,9 +213,12 @@ int x265amd_encoder::runFrame(const PicP& picp, std::shared_future<int> prev)
         tuRecs.cur = pic.tuRecs.data();
         for (int l = 0; l < 2; l++) if (!pic.lists[l].empty() && pic.lists[l][0]->tuRecs.size() == pic.tuRecs.size()) tuRecs.ref[l] = pic.lists[l][0]->tuRecs.data();
     }
+    x265amd_rskip_edge edge = { nullptr, 0, 0.0f };
+    const bool useEdge = p.recursionSkipMode == 2;          /* (an I picture never asks: its record goes in without counts) */
+    if (useEdge && si.slice_type != 2) { const int erc = edgeCounts(pic, st, edge); if (erc != X265AMD_OK) return erc; }
     int rc = xa_analyse_frame(me, st, &info, &sp, &si, &ap, pic.units.data(), pic.motion.data(), colPic ? colPic->motion.data() : noCol.data(),
                               refDepth.data(), refQp0.data(), planes.data(), (int)(planes.size() / 3), stride, cstride, stat.data(), coeff.data(), nullptr,
-                              sao ? nullptr : data.data(), data.size(), sizes.data(), &nsub, nullptr, useDqp ? pic.cuQp.data() : nullptr, p.limitTU >= 3 ? &tuRecs : nullptr);
+                              sao ? nullptr : data.data(), data.size(), sizes.data(), &nsub, nullptr, useDqp ? pic.cuQp.data() : nullptr, p.limitTU >= 3 ? &tuRecs : nullptr, useEdge ? &edge : nullptr);
     if (rc != X265AMD_OK) return rc;
     if (hipStreamSynchronize(st) != hipSuccess) return xa_fail(X265AMD_EHIP, "encoder: analysis");
 
@@ -763,9 +781,12 @@ int x265amd_encoder::runFrameParallel(const PicP& picp)
         tuRecs.cur = pic.tuRecs.data();
         for (int l = 0; l < 2; l++) if (!lists[l].empty() && lists[l][0]->tuRecs.size() == pic.tuRecs.size()) tuRecs.ref[l] = lists[l][0]->tuRecs.data();
     }
+    x265amd_rskip_edge edge = { nullptr, 0, 0.0f };
+    const bool useEdge = p.recursionSkipMode == 2;
+    if (useEdge && fc.si.slice_type != 2) { const int erc = edgeCounts(pic, st, edge); if (erc != X265AMD_OK) { pic.fail(); filters.join(); return rc = erc; } }
     int arc = xa_analyse_frame(me, st, &fc.info, &fc.sp, &fc.si, &fc.ap, pic.units.data(), pic.motion.data(), colPic ? colPic->motion.data() : noCol.data(),
                                refDepth.data(), refQp0.data(), fc.planes.data(), (int)(fc.planes.size() / 3), stride, cstride, stat.data(), coeff.data(), nullptr,
-                               sao ? nullptr : data.data(), data.size(), sizes.data(), &nsub, &hooks, useDqp ? pic.cuQp.data() : nullptr, p.limitTU >= 3 ? &tuRecs : nullptr);
+                               sao ? nullptr : data.data(), data.size(), sizes.data(), &nsub, &hooks, useDqp ? pic.cuQp.data() : nullptr, p.limitTU >= 3 ? &tuRecs : nullptr, useEdge ? &edge : nullptr);
     if (arc != X265AMD_OK) pic.fail();
     filters.join();
     if (arc != X265AMD_OK) return rc = arc;

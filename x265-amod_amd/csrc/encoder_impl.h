@@ -122,6 +122,7 @@ struct Pic
     bool weighted = false;                                 /* some reference of this slice carries a weight */
     bool bScenecut = false, bKeyframe = false;
     std::vector<int8_t> tuRecs;         /* --limit-tu 3 / 4: CUData::m_refTuDepth of every CTU (XaTuRecs) */
+    uint32_t* edgeCounts = nullptr;     /* --rskip 2, P / B pictures: Frame::m_edgeBitPic as the ones of every 32x32 block (mapped host memory the device pass writes; x265amd_encoder::edgeCounts) */
     /* ---- rate control other than constant QP (round 6): what adaptive quantisation and cuTree keep of a picture's Lowres (common/lowres.h) ---- */
     std::vector<int32_t> intraCostHost;                     /* Lowres::intraCost per lowres block (read back once, in lowresInit) */
     std::vector<double> qpAqOffset, qpCuTreeOffset;         /* Lowres::qpAqOffset / qpCuTreeOffset per 16x16 block (the lowres block grid) */
@@ -146,7 +147,7 @@ struct Pic
     }
     Pic() { memset(refPoc, 0, sizeof(refPoc)); memset(wp, 0, sizeof(wp)); for (int i = 0; i < 18; i++) { costEst[i] = -1; intraMbs[i] = 0; specIntraMbs[i] = 0; for (int j = 0; j < 18; j++) cost2[i][j] = specCost2[i][j] = -1; } }
     ~Pic() { if (pool) { for (auto& e : dLc) pool->put(e.second); for (auto& e : dSpecLc) pool->put(e.second);
-                         for (int i = 0; i < 18; i++) for (const std::vector<int16_t>* v : { &lowMvs[i], &lowMvs1[i], &specMvs[i], &specMvs1[i] }) if (!v->empty()) pool->dead(v->data()); } if (regMotion) xa_devmap_unregister(regMotion); xa_scratch_free(dSrc); xa_scratch_free(dRec); xa_scratch_free(dFin); xa_scratch_free(dLowres); xa_scratch_free(dIntraCost); for (volatile uint64_t* c : finalX) xa_counter_free(c); }
+                         for (int i = 0; i < 18; i++) for (const std::vector<int16_t>* v : { &lowMvs[i], &lowMvs1[i], &specMvs[i], &specMvs1[i] }) if (!v->empty()) pool->dead(v->data()); } if (regMotion) xa_devmap_unregister(regMotion); xa_scratch_free(dSrc); xa_scratch_free(dRec); xa_scratch_free(dFin); xa_scratch_free(dLowres); xa_scratch_free(dIntraCost); if (edgeCounts) xa_mapped_free(edgeCounts); for (volatile uint64_t* c : finalX) xa_counter_free(c); }
     void publish(int row, int x)
     {
         std::atomic_thread_fence(std::memory_order_release); *finalX[row] = (uint64_t)x;
@@ -240,6 +241,7 @@ struct x265amd_encoder
     int prepare(const PicP& pic);
     int runFrame(const PicP& pic, std::shared_future<int> prev);
     int runFrameParallel(const PicP& pic);
+    int edgeCounts(Pic& pic, hipStream_t st, x265amd_rskip_edge& edge);
     /* ---- the lookahead (slicetype.cpp): only when param.scenecutThreshold > 0 ---- */
     bool lookahead = false;
     void* wpEnergy = nullptr; void* wpSums = nullptr; void* wpSumsHost = nullptr; void* wpMvs = nullptr;      /* weighted prediction's device / mapped buffers: the encoder's for good (never back to the pools) */

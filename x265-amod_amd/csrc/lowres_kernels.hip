@@ -982,6 +982,51 @@ extern "C" int x265amd_aq_edge(void* stream, uint64_t luma, intptr_t stride, int
     return xa_aq_edge(stream, luma, stride, width, height, qg_size, d_density, d_avg_angle, d_wp, d_wp + 1, edge_plane, theta_plane);
 }
 
+/* ---------------- the edge-based recursion skip (--rskip 2): computeEdge on the SOURCE picture, counted per 32x32 block ----------------
+ * (frameencoder.cpp:474-484 -> slicetype.cpp:98-157 with no angle plane and white pixel 1; read by Analysis::complexityCheckCU, analysis.cpp:3561-3577).  The bit plane
+ * is 1 where the 3x3 Sobel of the source reaches the threshold, inside a border of one sample that stays 0; the analysis only ever asks for the plane's sum over a
+ * whole 32x32 or 64x64 CU (the plane holds 0 / 1: sum and sum of squares are both the number of ones), so the plane itself is never stored: what leaves the device is
+ * one count per 32x32 block.
+ * One workgroup per block: the 34 x 34 source tile (halo of one sample; 0 beyond the picture, where nothing that counts reads it) in LDS, four samples per lane,
+ * a wave reduction, the four waves' sums through LDS, one store.  Integer VALU only (xa_edge_is_edge, aq_edge_dev.h); a source sample is read 1.13 times. */
+constexpr int kRskipTile = 32;
+__global__ __launch_bounds__(256) void k_rskip_edge_counts(const pixel* src, long stride, int width, int height, int blocksW, uint32_t* counts)
+{
+    __shared__ uint16_t s[kRskipTile + 2][kRskipTile + 4];
+    __shared__ uint32_t waveSum[4];
+    const int tid = threadIdx.x, x0 = blockIdx.x * kRskipTile, y0 = blockIdx.y * kRskipTile;
+    for (int i = tid; i < (kRskipTile + 2) * (kRskipTile + 2); i += 256)
+    {
+        const int r = i / (kRskipTile + 2), c = i - r * (kRskipTile + 2), x = x0 - 1 + c, y = y0 - 1 + r;
+        s[r][c] = x >= 0 && y >= 0 && x < width && y < height ? (uint16_t)src[(long)y * stride + x] : (uint16_t)0;
+    }
+    __syncthreads();
+    uint32_t ones = 0;
+#pragma unroll
+    for (int i = 0; i < 4; i++)
+    {
+        const int px = tid & 31, py = (tid >> 5) + 8 * i, x = x0 + px, y = y0 + py;
+        if (x < 1 || y < 1 || x >= width - 1 || y >= height - 1) continue;
+        const int tl = s[py][px], tc = s[py][px + 1], tr = s[py][px + 2], ml = s[py + 1][px], mr = s[py + 1][px + 2], bl = s[py + 2][px], bc = s[py + 2][px + 1], br = s[py + 2][px + 2];
+        const int gh = -3 * tl + 3 * tr - 10 * ml + 10 * mr - 3 * bl + 3 * br;
+        const int gv = -3 * tl - 10 * tc - 3 * tr + 3 * bl + 10 * bc + 3 * br;
+        ones += (uint32_t)xa_edge_is_edge(gv, gh, XA_PIXEL_MAX);
+    }
+    ones = xa_wave_sum(ones);
+    if ((tid & 63) == 0) waveSum[tid >> 6] = ones;
+    __syncthreads();
+    if (tid == 0) counts[(size_t)blockIdx.y * blocksW + blockIdx.x] = waveSum[0] + waveSum[1] + waveSum[2] + waveSum[3];
+}
+extern "C" int x265amd_rskip_edge_counts(void* stream, uint64_t luma, intptr_t stride, int width, int height, uint32_t* d_counts)
+{
+    if (!luma || !d_counts || width <= 0 || height <= 0 || stride < width) return xa_fail(X265AMD_EINVAL, "x265amd_rskip_edge_counts: bad arguments");
+    const int bw = (width + kRskipTile - 1) / kRskipTile, bh = (height + kRskipTile - 1) / kRskipTile;
+    hipLaunchKernelGGL(k_rskip_edge_counts, dim3(bw, bh), dim3(256), 0, (hipStream_t)stream, (const pixel*)(uintptr_t)luma, (long)stride, width, height, bw, d_counts);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return xa_fail(X265AMD_EHIP, hipGetErrorString(e));
+    return X265AMD_OK;
+}
+
 /* the per-sample arithmetic of k_aq_edge on given gradient pairs: what the device makes of aq_edge_dev.h, to be held against the host's copy (x265amd_aq_edge_angles) */
 __global__ __launch_bounds__(256) void k_aq_edge_angles(const int32_t* gv, const int32_t* gh, int count, int32_t* theta, int32_t* edge)
 {

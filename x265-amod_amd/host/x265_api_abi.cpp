@@ -16,6 +16,7 @@
 #include "../../include/x265amd.h"
 #include "../../include/x265amd_encoder.h"
 #include "x265_abi_layout.h"
+#include "x265_abi_layout_rskip.h"
 #include "x265_api_table.h"
 #include <stdint.h>
 #include <stdio.h>
@@ -74,7 +75,7 @@ void abi_param_default(void* p)
     wr<int32_t>(p, X265ABI_PARAM_recursionSkipMode, 1); wr<int32_t>(p, X265ABI_PARAM_bEnableSignHiding, 1); wr<int32_t>(p, X265ABI_PARAM_bEnableStrongIntraSmoothing, 1);
     wr<int32_t>(p, X265ABI_PARAM_bEnableTemporalMvp, 1); wr<int32_t>(p, X265ABI_PARAM_bEnableLoopFilter, 1); wr<int32_t>(p, X265ABI_PARAM_bEnableSAO, 1);
     wr<int32_t>(p, X265ABI_PARAM_rdLevel, 3); wr<int32_t>(p, X265ABI_PARAM_bIntraInBFrames, 1); wr<double>(p, X265ABI_PARAM_psyRd, 2.0); wr<double>(p, X265ABI_PARAM_psyRdoq, 0.0);
-    wr<int32_t>(p, X265ABI_PARAM_bEmitCLL, 1);
+    wr<int32_t>(p, X265ABI_PARAM_bEmitCLL, 1); wr<float>(p, X265ABI_PARAM_edgeVarThreshold, 0.05f);
     wr<int32_t>(p, X265ABI_PARAM_vui_videoFormat, 5); wr<int32_t>(p, X265ABI_PARAM_vui_colorPrimaries, 2); wr<int32_t>(p, X265ABI_PARAM_vui_transferCharacteristics, 2);
     wr<int32_t>(p, X265ABI_PARAM_vui_matrixCoeffs, 2);         /* unspecified (param.cpp:358-366) */
     wr<int32_t>(p, X265ABI_PARAM_rc_rateControlMode, 2 /* X265_RC_CRF */); wr<int32_t>(p, X265ABI_PARAM_rc_qp, 32); wr<double>(p, X265ABI_PARAM_rc_ipFactor, 1.4f);
@@ -224,6 +225,9 @@ int abi_param_parse(void* p, const char* name, const char* value)
         { "ipratio", X265ABI_PARAM_rc_ipFactor }, { "pbratio", X265ABI_PARAM_rc_pbFactor } };
     for (const auto& it : reals)
         if (!strcmp(key, it.name)) { const double v = real(bad); wr<double>(p, it.off, v); return bad ? -2 : 0; }
+    /* (param.cpp:1280: atoi(value) / 100.0f -- which the reference's -ffast-math build computes as a float product with 0.01f: "5" gives 0.049999997f, one ulp below the
+     * default 0.05f) */
+    if (!strcmp(key, "rskip-edge-threshold")) { const int v = num(bad); wr<float>(p, X265ABI_PARAM_edgeVarThreshold, (float)v * 0.01f); return bad ? -2 : 0; }
     if (!strcmp(key, "crf")) { const double v = real(bad); if (bad) return -2; wr<double>(p, X265ABI_PARAM_rc_rfConstant, v); wr<int32_t>(p, X265ABI_PARAM_rc_rateControlMode, 2); return 0; }
     if (!strcmp(key, "qp")) { const int v = num(bad); if (bad) return -2; wr<int32_t>(p, X265ABI_PARAM_rc_qp, v); wr<int32_t>(p, X265ABI_PARAM_rc_rateControlMode, 1); return 0; }
     if (!strcmp(key, "bitrate")) { const int v = num(bad); if (bad) return -2; wr<int32_t>(p, X265ABI_PARAM_rc_bitrate, v); wr<int32_t>(p, X265ABI_PARAM_rc_rateControlMode, 0); return 0; }
@@ -397,7 +401,7 @@ void* abi_encoder_open(void* p)
     q.bEmitInfoSEI = PI(p, bEmitInfoSEI) != 0; q.bRepeatHeaders = PI(p, bRepeatHeaders) != 0; q.qpMin = PI(p, rc_qpMin); q.qpMax = PI(p, rc_qpMax);
     /* (Encoder::configure's rules for these switches, encoder.cpp:3721-3754, are x265amd_encoder_open's) */
     q.rdLevel = PI(p, rdLevel); q.bEnableRectInter = PI(p, bEnableRectInter); q.bEnableAMP = PI(p, bEnableAMP); q.limitModes = PI(p, limitModes); q.limitReferences = PI(p, limitReferences);
-    q.bEnableEarlySkip = PI(p, bEnableEarlySkip); q.recursionSkipMode = PI(p, recursionSkipMode); q.bIntraInBFrames = PI(p, bIntraInBFrames); q.psyRd = PD(p, psyRd);
+    q.bEnableEarlySkip = PI(p, bEnableEarlySkip); q.recursionSkipMode = PI(p, recursionSkipMode); q.edgeVarThreshold = rd<float>(p, X265ABI_PARAM_edgeVarThreshold); q.bIntraInBFrames = PI(p, bIntraInBFrames); q.psyRd = PD(p, psyRd);
     q.searchMethod = PI(p, searchMethod); q.subpelRefine = PI(p, subpelRefine); q.searchRange = PI(p, searchRange); q.maxNumMergeCand = PI(p, maxNumMergeCand);
     q.bEnableSignHiding = PI(p, bEnableSignHiding); q.bEnableStrongIntraSmoothing = PI(p, bEnableStrongIntraSmoothing); q.bEnableTemporalMvp = PI(p, bEnableTemporalMvp);
     q.tuQTMaxInterDepth = PI(p, tuQTMaxInterDepth); q.tuQTMaxIntraDepth = PI(p, tuQTMaxIntraDepth);

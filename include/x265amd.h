@@ -1189,6 +1189,50 @@ int x265amd_analyse_frame_ex(x265amd_me_ctx* me, void* stream, const x265amd_mvp
                              intptr_t stride, intptr_t cstride, x265amd_cu_stat* cu_stat, int16_t* coeff_out, x265amd_ctu_result* results,
                              uint8_t* slice_data, size_t cap, uint32_t* substream_sizes, int* num_substreams, const x265amd_rskip_edge* edge);
 
+/* Histogram-based scene-cut detection (--hist-scenecut: param.bHistBasedSceneCut; 8-bit samples only).
+ * x265amd_hist_scene_stats = what LookaheadTLD::collectPictureStatistics measures of a source picture at the CODED size (width x height, multiples of 8, 32 at least), as raw
+ * numbers (reference: source/common/lowres.cpp:35-51 and :392-402, source/encoder/slicetype.cpp:1441-1724):
+ *   counts[wi * 4 + hi][0]   the 256-bin histogram of segment (wi, hi) of the QUARTER picture -- frame_lowres_core of the half-size full-pel plane, width / 4 x height / 4 samples;
+ *                            4 x 4 segments of (width / 4) / 4 x (height / 4) / 4 samples, the last column and row taking the remainder
+ *   counts[..][1], [..][2]   the histograms of Cb and Cr over the same grid in full-resolution units (width / 4 x height / 4, remainder to the last), origin and size halved
+ *                            with >> 1, every 4th sample of every 4th row
+ *   sums[..][c]              the sum of the samples counted
+ *   bands (behind the struct: uint64_t [3][height / 8])   per plane and per row of blocks -- 8x8 luma, 4x4 chroma -- the sum over the row's blocks of ssd - (sum * sum >> 6 or 4)
+ * planes: HOST array of the device addresses of sample (0,0) of Y, Cb, Cr; half: device address of sample (0,0) of the half-size plane x265amd_lowres_init made of the picture.
+ * d_record: device memory of X265AMD_HIST_SCENE_RECORD_BYTES(height) bytes, zeroed and filled by the call; quarter_plane: 0, or the device address of width / 4 x height / 4
+ * samples that take the quarter picture.  Integer atomics only: the record does not depend on the order of arrival.  Asynchronous.
+ * x265amd_hist_scene_model: the same record and quarter picture in host code from host planes. */
+typedef struct x265amd_hist_scene_record { uint32_t counts[16][3][256]; uint64_t sums[16][3]; } x265amd_hist_scene_record;
+#define X265AMD_HIST_SCENE_RECORD_BYTES(height) (sizeof(x265amd_hist_scene_record) + (size_t)3 * ((height) / 8) * sizeof(uint64_t))
+int x265amd_hist_scene_stats(void* stream, const uint64_t planes[3], intptr_t stride, intptr_t cstride, uint64_t half, intptr_t half_stride, int width, int height,
+                             x265amd_hist_scene_record* d_record, uint64_t quarter_plane);
+int x265amd_hist_scene_model(const x265amd_pixel* const planes[3], intptr_t stride, intptr_t cstride, const x265amd_pixel* half, intptr_t half_stride, int width, int height,
+                             x265amd_hist_scene_record* record, x265amd_pixel* quarter);
+/* x265amd_hist_scene_finish: a record -> what the reference keeps in Lowres (bins (1 + count) << 4; the (uint8_t) quotients of slicetype.cpp:1619, :1639, :1688, :1717-1719 as
+ * spelt there; picAvgVariance* = (uint16_t)(sum over bands of (uint16_t)(band / maxCol) / maxRow) with the plane's width and height in samples, :1486-1489). */
+typedef struct x265amd_hist_scene_pic
+{
+    uint32_t picHistogram[4][4][3][256];
+    uint8_t averageIntensityPerSegment[4][4][3];
+    uint8_t averageIntensity[3];
+    uint16_t picAvgVariance, picAvgVarianceCb, picAvgVarianceCr;
+} x265amd_hist_scene_pic;
+int x265amd_hist_scene_finish(const x265amd_hist_scene_record* record, int width, int height, x265amd_hist_scene_pic* out);
+/* x265amd_hist_scene_change = Lookahead::detectHistBasedSceneChange (slicetype.cpp:3057-3188) on the picture before, the picture and the picture behind it: 1 = scene change,
+ * 0 = none, negative = bad arguments.  state: what the Lookahead object carries from call to call (x265amd_hist_scene_state_init: slicetype.cpp:1072-1095).  verdicts: NULL, or
+ * 16 words [wi * 4 + hi]: 0 = no abrupt change in the segment, else X265AMD_HIST_* in the low byte and the three numbers of the reference's debug line above it
+ * (future-past << 8, future-present << 16, present-past << 24). */
+typedef struct x265amd_hist_scene_state
+{
+    uint32_t accHistDiffRunningAvg[4][4], accHistDiffRunningAvgCb[4][4], accHistDiffRunningAvgCr[4][4];
+    int32_t resetRunningAvg;
+    uint32_t segmentCountThreshold;
+} x265amd_hist_scene_state;
+enum { X265AMD_HIST_FLASH = 1, X265AMD_HIST_FADE = 2, X265AMD_HIST_INTENSITY = 3, X265AMD_HIST_SCENE = 4 };
+void x265amd_hist_scene_state_init(x265amd_hist_scene_state* state);
+int x265amd_hist_scene_change(const x265amd_hist_scene_pic* previous, const x265amd_hist_scene_pic* current, const x265amd_hist_scene_pic* future, int width, int height,
+                              x265amd_hist_scene_state* state, int32_t* verdicts);
+
 /* returns the device scratch the host orchestrators keep between calls (a size-class pool) to the HIP runtime */
 void x265amd_release_scratch(void);
 /* X265AMD_HOSTPROF=1: prints (stderr) the host CPU time by named scope collected so far (development aid) */

@@ -118,7 +118,11 @@ typedef struct x265amd_param
                                              * analysis.cpp:3712) */
     int32_t bRepeatHeaders;                 /* param.bRepeatHeaders (--repeat-headers; Encoder::configure switches it on for all-intra encodes, --keyint 1): VPS / SPS / PPS in front
                                              * of every keyframe's slice units (Encoder::encode, encoder.cpp:2035-2045) */
-    int32_t reserved2;
+    int32_t bHistBasedSceneCut;             /* param.bHistBasedSceneCut (--hist-scenecut; 0): the histogram-based scene-change detector in place of the cost-based one in the slice-type
+                                             * decision (Lookahead::histBasedScenecut / detectHistBasedSceneChange, slicetype.cpp:3057-3216, on the statistics of
+                                             * x265amd_hist_scene_stats per source picture); scenecutThreshold > 0 still says whether a detected change places an I picture.
+                                             * Switches the lookahead on; cleared for keyframeMax < 0 and <= 1.  8-bit library only, not with shardCount > 1.
+                                             * (The slot was a reserved int32 until the detector was built: same offset, same four bytes) */
     /* param.vui (x265.h: the video usability information of the SPS, Encoder::initSPS encoder.cpp:3388-3423; aspectRatioIdc is further up): signalling only, nothing here changes a
      * coded sample.  --sar W:H (aspectRatioIdc 255), --overscan, --videoformat, --range, --colorprim, --transfer, --colormatrix, --chromaloc, --display-window */
     int32_t vuiSarWidth, vuiSarHeight;

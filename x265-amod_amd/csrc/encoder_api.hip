@@ -83,12 +83,12 @@ extern "C" x265amd_encoder* x265amd_encoder_open(const x265amd_param* p)
      * aq-mode 1 at strength 0 (cuTree needs the offset arrays; delta QP is on); strength 0 without cuTree is no AQ at all */
     x265amd_param norm = *p;
     /* --keyint -1 (encoder.cpp:3627-3635): "only one I frame at the start of the stream": an infinite GOP distance and no adaptive I frame placement */
-    if (norm.keyframeMax < 0) { norm.keyframeMax = INT_MAX; norm.scenecutThreshold = 0; }
+    if (norm.keyframeMax < 0) { norm.keyframeMax = INT_MAX; norm.scenecutThreshold = 0; norm.bHistBasedSceneCut = 0; }
     if (norm.keyframeMax <= 1 && norm.keyframeMax >= 0)
     {
         /* all-intra encodes (encoder.cpp:3636-3658): no lookahead, no B pictures, no cuTree, no weights, one reference, the parameter sets with every picture */
         norm.keyframeMax = 1; norm.keyframeMin = 1; norm.bFrameAdaptive = 0; norm.bframes = 0; norm.bOpenGOP = 0; norm.bRepeatHeaders = 1; norm.lookaheadDepth = 0;
-        norm.scenecutThreshold = 0; norm.cuTree = 0; norm.bEnableWeightedPred = 0; norm.bEnableWeightedBiPred = 0; norm.maxNumReferences = 1;
+        norm.scenecutThreshold = 0; norm.bHistBasedSceneCut = 0; norm.cuTree = 0; norm.bEnableWeightedPred = 0; norm.bEnableWeightedBiPred = 0; norm.maxNumReferences = 1;
     }
     /* the HDR10 SEI units come with the parameter sets at every keyframe ("Turning on repeat-headers for HDR compatibility", encoder.cpp:4347-4353) */
     if (norm.bEmitHDR10SEI || norm.hasMasteringDisplay || norm.maxCLL || norm.maxFALL) { norm.bEmitHDR10SEI = 1; norm.bRepeatHeaders = 1; }
@@ -146,6 +146,9 @@ extern "C" x265amd_encoder* x265amd_encoder_open(const x265amd_param* p)
         XA_REQUIRE(p->recursionSkipMode != 2 || p->aqMode < 4, "recursionSkipMode 2 with aqMode 4 / 5 is not built (the bit plane would come from the filtered edge picture)");
         XA_REQUIRE(p->recursionSkipMode != 2 || (p->edgeVarThreshold >= 0.0f && p->edgeVarThreshold <= 1.0f), "edgeVarThreshold outside 0..1 (--rskip-edge-threshold 0..100)");
         XA_REQUIRE(p->recursionSkipMode != 2 || p->shardCount <= 1, "recursionSkipMode 2 with pictures coded on several GPUs (shardCount > 1) is not built");
+        /* histogram scene-cut detection: the reference indexes its 256 bins with 10-bit samples (the planes' bins overlap inside its allocation), which is not restated */
+        XA_REQUIRE(!p->bHistBasedSceneCut || X265AMD_DEPTH == 8, "bHistBasedSceneCut: histogram scene-cut detection is built for the 8-bit library only");
+        XA_REQUIRE(!p->bHistBasedSceneCut || p->shardCount <= 1, "bHistBasedSceneCut with pictures coded on several GPUs (shardCount > 1) is not built");
         XA_REQUIRE(p->limitReferences >= 0 && p->limitReferences <= 3, "limitReferences outside 0..3");
         XA_REQUIRE(!p->bEnableAMP || p->bEnableRectInter, "bEnableAMP needs bEnableRectInter");
 #undef XA_REQUIRE
@@ -182,7 +185,8 @@ extern "C" x265amd_encoder* x265amd_encoder_open(const x265amd_param* p)
     if (p->shardCount < 0 || p->shardCount > 64 || (p->shardCount > 1 && (p->shardRank < 0 || p->shardRank >= p->shardCount || p->frameNumThreads <= 1)))
     { xa_fail(X265AMD_EINVAL, "encoder_open: shardRank / shardCount (frame-per-GPU needs 0 <= rank < count and frameNumThreads > 1: rows are published by pictures coded in parallel)"); return nullptr; }
     if (p->bFrameAdaptive < 0 || p->bFrameAdaptive > 2) { xa_fail(X265AMD_EINVAL, "encoder_open: bFrameAdaptive: 0 (fixed mini-GOPs), 1 (fast) or 2 (trellis)"); return nullptr; }
-    e->lookahead = p->scenecutThreshold > 0 || (p->bFrameAdaptive && p->bframes) || p->cuTree || p->aqMode;
+    e->lookahead = p->scenecutThreshold > 0 || p->bHistBasedSceneCut || (p->bFrameAdaptive && p->bframes) || p->cuTree || p->aqMode;          /* (slicetype.cpp:1909-1912) */
+    x265amd_hist_scene_state_init(&e->histState);
     if ((p->bEnableWeightedPred || p->bEnableWeightedBiPred) && !e->lookahead) { xa_fail(X265AMD_EINVAL, "encoder_open: bEnableWeightedPred needs the lookahead (scenecutThreshold > 0 or bFrameAdaptive 2 with B frames)"); return nullptr; }
     {
         /* Encoder::configure (encoder.cpp:3658-3663) */

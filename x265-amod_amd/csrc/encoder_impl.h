@@ -122,6 +122,8 @@ struct Pic
     bool weighted = false;                                 /* some reference of this slice carries a weight */
     bool bScenecut = false, bKeyframe = false;
     std::vector<int8_t> tuRecs;         /* --limit-tu 3 / 4: CUData::m_refTuDepth of every CTU (XaTuRecs) */
+    std::unique_ptr<x265amd_hist_scene_pic> hist;          /* --hist-scenecut: what LookaheadTLD::collectPictureStatistics leaves in Lowres (x265amd_hist_scene_finish; lowresInit) */
+    bool bHistScenecutAnalyzed = false;                    /* Lowres::bHistScenecutAnalyzed */
     uint32_t* edgeCounts = nullptr;     /* --rskip 2, P / B pictures: Frame::m_edgeBitPic as the ones of every 32x32 block (mapped host memory the device pass writes; x265amd_encoder::edgeCounts) */
     /* ---- rate control other than constant QP (round 6): what adaptive quantisation and cuTree keep of a picture's Lowres (common/lowres.h) ---- */
     std::vector<int32_t> intraCostHost;                     /* Lowres::intraCost per lowres block (read back once, in lowresInit) */
@@ -230,6 +232,8 @@ struct x265amd_encoder
         if (dSaoParams) (void)hipFree(dSaoParams);
         if (dDbUnits) (void)hipFree(dDbUnits);
         xa_scratch_free(dSaoTmp);
+        xa_scratch_free(histRecord);
+        if (histRecordHost) xa_mapped_free(histRecordHost);
         if (laStream) (void)hipStreamDestroy(laStream);
         if (importStream) (void)hipStreamDestroy(importStream);
     }
@@ -286,6 +290,11 @@ struct x265amd_encoder
     void extendPlans(std::vector<Pic*>& frames, int length, std::vector<std::vector<uint8_t> >& plans, int& rc);
     bool scenecutInternal(std::vector<Pic*>& frames, int p0, int p1, bool real, int& rc);
     bool scenecut(std::vector<Pic*>& frames, int p0, int p1, bool real, int numFrames, int& rc);
+    /* --hist-scenecut (param.bHistBasedSceneCut): the device record of x265amd_hist_scene_stats and its host copy (the encoder's: lowresInit waits before it returns), what
+     * the Lookahead object carries between calls of detectHistBasedSceneChange, and Lookahead::histBasedScenecut */
+    void* histRecord = nullptr; void* histRecordHost = nullptr;
+    x265amd_hist_scene_state histState;
+    bool histBasedScenecut(std::vector<Pic*>& frames, int p0, int p1, int numFrames);
     int slicetypeAnalyse(std::vector<Pic*>& frames, bool bKeyframe = false);
     int decideLookahead(bool flush, int maxGops = 1 << 30);
     /* ---- rate control other than constant QP (round 6; include/x265amd_ratecontrol.h) ---- */

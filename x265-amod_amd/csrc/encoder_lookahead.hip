@@ -35,9 +35,27 @@ int x265amd_encoder::lowresInit(Pic& pic)
         if (rc != X265AMD_OK) return rc;
     }
     if (aqOn && (rc = adaptiveQuant(pic)) != X265AMD_OK) return rc;
+    if (p.bHistBasedSceneCut)
+    {
+        /* LookaheadTLD::collectPictureStatistics, where PreLookaheadGroup::processTasks runs it (slicetype.cpp:1743-1744): behind calcAdaptiveQuantFrame, in front of the
+         * intra estimate's results.  The record comes back with the intra costs, behind the one wait of this function */
+        const size_t bytes = X265AMD_HIST_SCENE_RECORD_BYTES(H);
+        if (!histRecord && (xa_scratch_alloc(&histRecord, bytes) != hipSuccess || xa_mapped_alloc(&histRecordHost, bytes, true) != hipSuccess))
+            return xa_fail(X265AMD_EHIP, "encoder_encode: device allocation");
+        const uint64_t srcP[3] = { planeAddr(pic.dSrc, 0), planeAddr(pic.dSrc, 1), planeAddr(pic.dSrc, 2) };
+        rc = x265amd_hist_scene_stats(laStream, srcP, stride, cstride, (uint64_t)(uintptr_t)planes[0], lowStride, W, H, (x265amd_hist_scene_record*)histRecord, 0);
+        if (rc != X265AMD_OK) return rc;
+        if (hipMemcpyAsync(histRecordHost, histRecord, bytes, hipMemcpyDeviceToHost, laStream) != hipSuccess) return xa_fail(X265AMD_EHIP, "encoder_encode: picture statistics");
+    }
     std::vector<int32_t> ic((size_t)lowCuW * lowCuH);
     if (hipMemcpyAsync(ic.data(), pic.dIntraCost, ic.size() * 4, hipMemcpyDeviceToHost, laStream) != hipSuccess || hipStreamSynchronize(laStream) != hipSuccess)
         return xa_fail(X265AMD_EHIP, "encoder_encode: lowres intra costs");
+    if (p.bHistBasedSceneCut)
+    {
+        pic.hist.reset(new x265amd_hist_scene_pic);
+        if (x265amd_hist_scene_finish((const x265amd_hist_scene_record*)histRecordHost, W, H, pic.hist.get()) != X265AMD_OK) return xa_fail(X265AMD_EINVAL, "encoder_encode: picture statistics");
+        pic.bHistScenecutAnalyzed = false;
+    }
     if (aqOn)
     {
         /* the rest of calcAdaptiveQuantFrame (slicetype.cpp:513-640) on the block energies that have arrived with the intra costs */
@@ -701,6 +719,25 @@ bool x265amd_encoder::scenecut(std::vector<Pic*>& frames, int p0, int p1, bool r
     return scenecutInternal(frames, p0, p1, real, rc);
 }
 
+/* Lookahead::histBasedScenecut (slicetype.cpp:3190-3216): the pictures of the first mini-GOP that have not been looked at yet, each with the picture before and the picture
+ * behind it; `frames` ends where the reference's array has its NULL */
+bool x265amd_encoder::histBasedScenecut(std::vector<Pic*>& frames, int p0, int p1, int numFrames)
+{
+    if (p.bframes)
+    {
+        const int maxp1 = std::min(p0 + 1 + p.bframes, numFrames);
+        for (int cp1 = p0; cp1 < maxp1; cp1++)
+        {
+            if (frames[cp1 + 1]->bHistScenecutAnalyzed) continue;
+            if (cp1 + 2 >= (int)frames.size()) continue;
+            Pic* prev = frames[cp1]; Pic* cur = frames[cp1 + 1]; Pic* next = frames[cp1 + 2];
+            cur->bHistScenecutAnalyzed = true;
+            if (x265amd_hist_scene_change(prev->hist.get(), cur->hist.get(), next->hist.get(), W, H, &histState, nullptr) == 1) cur->bScenecut = true;
+        }
+    }
+    return frames[p1]->bScenecut;
+}
+
 /* Lookahead::slicetypeAnalyse(frames, bKeyframe) (slicetype.cpp:2603-2919) without VBV / zones / gop-lookahead: frames[0] = the last non-B picture, frames[1..] = the
  * undecided pictures of the window.  bKeyframe: the pass behind a keyframe's mini-GOP that cuTree adds (slicetype.cpp:2469-2483): the same analysis with the keyframe as
  * frames[0], cuTree down to the keyframe itself, and every type taken back afterwards */
@@ -789,7 +826,8 @@ int x265amd_encoder::slicetypeAnalyse(std::vector<Pic*>& frames, bool bKeyframe)
         rc = frameCostMany(jobs);
         if (rc != X265AMD_OK) return rc;
     }
-    const bool isScenecut = scenecut(frames, 0, 1, true, origNumFrames, rc);       /* (run whatever the threshold: its estimates and marks stay) */
+    /* (the cost-based check runs whatever the threshold: its estimates and marks stay.  Under --hist-scenecut it does not run at all, slicetype.cpp:2742-2745) */
+    const bool isScenecut = p.bHistBasedSceneCut ? histBasedScenecut(frames, 0, 1, origNumFrames) : scenecut(frames, 0, 1, true, origNumFrames, rc);
     if (rc != X265AMD_OK) return rc;
     if (p.scenecutThreshold > 0 && isScenecut) { frames[1]->type = TYPE_I; return X265AMD_OK; }
     int resetStart;

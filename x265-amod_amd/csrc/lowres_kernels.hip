@@ -1027,6 +1027,107 @@ extern "C" int x265amd_rskip_edge_counts(void* stream, uint64_t luma, intptr_t s
     return X265AMD_OK;
 }
 
+/* ---------------- histogram-based scene-cut detection (--hist-scenecut): the per-picture statistics ----------------
+ * (LookaheadTLD::collectPictureStatistics, slicetype.cpp:1441-1724, and the quarter picture of Lowres::init, lowres.cpp:392-402; the host half is host/hist_scenecut.cpp.)
+ * Two kernels behind one entry point, both into one record that the entry point zeroes first:
+ *   k_hist_scene_hist   grid (16 segments, row chunks, 3 planes).  A workgroup counts kHistRows rows of its segment's SAMPLED grid -- plane 0: the quarter picture, every
+ *                       sample formed from four of the half-size plane where it is counted (and stored when a plane is asked for); planes 1 / 2: every 4th sample of every 4th row
+ *                       of the chroma region -- into a 256-bin LDS histogram, then adds every non-empty bin and the chunk's sum to the record: integer atomics, so the
+ *                       record is the same whatever order the workgroups arrive in.
+ *   k_hist_scene_bands  grid (height / 8 bands, 3 planes).  A lane takes 8x8 luma / 4x4 chroma blocks of its band, ssd - (sum * sum >> 6 or 4) each in uint32_t as
+ *                       acEnergyVarHist returns it; one 64-bit sum per band, stored (no atomics: one workgroup per band).
+ * 8-bit samples only: a 10-bit sample would index past the 256 bins (the entry point refuses). */
+constexpr int kHistRows = 8;
+__global__ __launch_bounds__(256) void k_hist_scene_hist(const pixel* half, long halfStride, const pixel* cb, const pixel* cr, long cstride, int width, int height,
+                                                         x265amd_hist_scene_record* rec, pixel* quarter)
+{
+    __shared__ uint32_t bins[256];
+    __shared__ uint32_t chunkSum;
+    const int tid = threadIdx.x, seg = blockIdx.x, wi = seg >> 2, hi = seg & 3, plane = blockIdx.z;
+    /* the segment's sampled grid: origin (gx, gy) and size nx x ny in samples of the plane that is counted, `step` apart */
+    int gx, gy, nx, ny, step;
+    if (plane == 0)
+    {
+        const int qw = width / 4, qh = height / 4, sw = qw / 4, sh = qh / 4;
+        gx = wi * sw; gy = hi * sh; nx = wi == 3 ? qw - 3 * sw : sw; ny = hi == 3 ? qh - 3 * sh : sh; step = 1;
+    }
+    else
+    {
+        const int sw = width / 4, sh = height / 4;
+        const int rw = (wi == 3 ? width - 3 * sw : sw) >> 1, rh = (hi == 3 ? height - 3 * sh : sh) >> 1;
+        gx = (wi * sw) >> 1; gy = (hi * sh) >> 1; nx = (rw + 3) >> 2; ny = (rh + 3) >> 2; step = 4;
+    }
+    const int row0 = blockIdx.y * kHistRows, row1 = min(row0 + kHistRows, ny);
+    if (row0 >= ny) return;          /* (the whole workgroup: the grid's chunk count is the tallest plane's) */
+    bins[tid] = 0;
+    if (tid == 0) chunkSum = 0;
+    __syncthreads();
+    uint32_t sum = 0;
+    const pixel* src = plane == 1 ? cb : cr;
+    for (int r = row0; r < row1; r++)
+        for (int c = tid; c < nx; c += 256)
+        {
+            uint32_t v;
+            if (plane == 0)
+            {
+                const int x = gx + c, y = gy + r;
+                const pixel* s0 = half + (long)(2 * y) * halfStride + 2 * x; const pixel* s1 = s0 + halfStride;
+                v = ((((uint32_t)s0[0] + s1[0] + 1) >> 1) + (((uint32_t)s0[1] + s1[1] + 1) >> 1) + 1) >> 1;
+                if (quarter) quarter[(long)y * (width / 4) + x] = (pixel)v;
+            }
+            else
+                v = src[(long)(gy + r * step) * cstride + gx + c * step];
+            atomicAdd(&bins[v & 255], 1u);
+            sum += v;
+        }
+    sum = xa_wave_sum(sum);
+    if ((tid & 63) == 0 && sum) atomicAdd(&chunkSum, sum);
+    __syncthreads();
+    if (bins[tid]) atomicAdd(&rec->counts[seg][plane][tid], bins[tid]);
+    if (tid == 0 && chunkSum) atomicAdd((unsigned long long*)&rec->sums[seg][plane], (unsigned long long)chunkSum);
+}
+__global__ __launch_bounds__(256) void k_hist_scene_bands(const pixel* luma, long stride, const pixel* cb, const pixel* cr, long cstride, int width, int height, uint64_t* bands)
+{
+    __shared__ uint64_t waveSum[4];
+    const int tid = threadIdx.x, band = blockIdx.x, plane = blockIdx.y;
+    const int size = plane ? 4 : 8, shift = plane ? 4 : 6, blocks = width / 8;          /* (width / 2) / 4 chroma blocks: the same number */
+    const pixel* src = plane == 0 ? luma : plane == 1 ? cb : cr;
+    const long st = plane ? cstride : stride;
+    uint64_t acc = 0;
+    for (int b = tid; b < blocks; b += 256)
+    {
+        const pixel* p = src + (long)(band * size) * st + b * size;
+        uint32_t sum = 0, ssd = 0;
+        for (int y = 0; y < size; y++)
+            for (int x = 0; x < size; x++) { const uint32_t v = p[y * st + x]; sum += v; ssd += v * v; }
+        acc += (uint32_t)(ssd - ((uint64_t)sum * sum >> shift));
+    }
+    acc = xa_wave_sum(acc);
+    if ((tid & 63) == 0) waveSum[tid >> 6] = acc;
+    __syncthreads();
+    if (tid == 0) bands[(size_t)plane * (height / 8) + band] = waveSum[0] + waveSum[1] + waveSum[2] + waveSum[3];
+}
+extern "C" int x265amd_hist_scene_stats(void* stream, const uint64_t planes[3], intptr_t stride, intptr_t cstride, uint64_t half, intptr_t half_stride, int width, int height,
+                                        x265amd_hist_scene_record* d_record, uint64_t quarter_plane)
+{
+    if (X265AMD_DEPTH != 8) return xa_fail(X265AMD_EINVAL, "x265amd_hist_scene_stats: histogram scene-cut detection is built for 8-bit samples only");
+    if (!planes || !planes[0] || !planes[1] || !planes[2] || !half || !d_record || width < 32 || height < 32 || (width & 7) || (height & 7) || stride < width || cstride < width / 2 ||
+        half_stride < width / 2)
+        return xa_fail(X265AMD_EINVAL, "x265amd_hist_scene_stats: bad arguments");
+    hipStream_t st = (hipStream_t)stream;
+    if (hipMemsetAsync(d_record, 0, X265AMD_HIST_SCENE_RECORD_BYTES(height), st) != hipSuccess) return xa_fail(X265AMD_EHIP, "x265amd_hist_scene_stats: memset");
+    /* the tallest sampled grid of a segment: the quarter picture's last row of segments (the chroma grids are (height / 4 + remainder) / 8 rows, never taller) */
+    const int qh = height / 4, tallest = qh - 3 * (qh / 4), chunks = (tallest + kHistRows - 1) / kHistRows;
+    const pixel* cb = (const pixel*)(uintptr_t)planes[1]; const pixel* cr = (const pixel*)(uintptr_t)planes[2];
+    hipLaunchKernelGGL(k_hist_scene_hist, dim3(16, chunks, 3), dim3(256), 0, st, (const pixel*)(uintptr_t)half, (long)half_stride, cb, cr, (long)cstride, width, height, d_record,
+                       (pixel*)(uintptr_t)quarter_plane);
+    hipLaunchKernelGGL(k_hist_scene_bands, dim3(height / 8, 3), dim3(256), 0, st, (const pixel*)(uintptr_t)planes[0], (long)stride, cb, cr, (long)cstride, width, height,
+                       (uint64_t*)(d_record + 1));
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return xa_fail(X265AMD_EHIP, hipGetErrorString(e));
+    return X265AMD_OK;
+}
+
 /* the per-sample arithmetic of k_aq_edge on given gradient pairs: what the device makes of aq_edge_dev.h, to be held against the host's copy (x265amd_aq_edge_angles) */
 __global__ __launch_bounds__(256) void k_aq_edge_angles(const int32_t* gv, const int32_t* gh, int count, int32_t* theta, int32_t* edge)
 {

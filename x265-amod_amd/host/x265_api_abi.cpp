@@ -195,7 +195,8 @@ int abi_param_parse(void* p, const char* name, const char* value)
         { "deblock", X265ABI_PARAM_bEnableLoopFilter }, { "sao", X265ABI_PARAM_bEnableSAO }, { "early-skip", X265ABI_PARAM_bEnableEarlySkip }, { "fast-intra", X265ABI_PARAM_bEnableFastIntra },
         { "b-intra", X265ABI_PARAM_bIntraInBFrames }, { "limit-modes", X265ABI_PARAM_limitModes }, { "cutree", X265ABI_PARAM_rc_cuTree }, { "info", X265ABI_PARAM_bEmitInfoSEI },
         { "annexb", X265ABI_PARAM_bAnnexB }, { "repeat-headers", X265ABI_PARAM_bRepeatHeaders }, { "aud", X265ABI_PARAM_bEnableAccessUnitDelimiters }, { "hdr10", X265ABI_PARAM_bEmitHDR10SEI },
-        { "hdr", X265ABI_PARAM_bEmitHDR10SEI }, { "cll", X265ABI_PARAM_bEmitCLL }, { "tskip", X265ABI_PARAM_bEnableTransformSkip }, { "lossless", X265ABI_PARAM_bLossless } };
+        { "hdr", X265ABI_PARAM_bEmitHDR10SEI }, { "cll", X265ABI_PARAM_bEmitCLL }, { "tskip", X265ABI_PARAM_bEnableTransformSkip }, { "lossless", X265ABI_PARAM_bLossless },
+        { "hist-scenecut", X265ABI_PARAM_bHistBasedSceneCut } };          /* (param.cpp:1279) */
     if (!strcmp(key, "deblock") && !neg && value)
     {
         /* --deblock tc:beta | tc,beta | tc | a truth value (param.cpp:1083-1097) */
@@ -371,7 +372,6 @@ void* abi_encoder_open(void* p)
     REQUIRE(!PI(p, rc_bEnableGrain), "rc.bEnableGrain (--tune grain): the grain rate control is not built");
     REQUIRE(PI(p, rc_vbvBufferSize) == 0 && !PI(p, rc_bStatRead) && !PI(p, rc_bStatWrite), "rc: VBV and multi-pass statistics are not built");
     REQUIRE(PI(p, bFrameAdaptive) >= 0 && PI(p, bFrameAdaptive) <= 2, "bFrameAdaptive (--b-adapt): 0, 1 or 2");
-    REQUIRE(!PI(p, bHistBasedSceneCut), "bHistBasedSceneCut: histogram scene-cut detection is not built");
     REQUIRE(PI(p, maxCUSize) == 64 && PI(p, minCUSize) == 8 && PI(p, maxTUSize) == 32, "maxCUSize / minCUSize / maxTUSize: only 64 / 8 / 32 are built");
     REQUIRE(!PI(p, interlaceMode) && !PI(p, bField), "interlaced coding is not built");
     REQUIRE(!PI(p, bLossless) && !PI(p, bCULossless), "lossless coding is not built");
@@ -394,7 +394,7 @@ void* abi_encoder_open(void* p)
     x265amd_param_default(&q);
     q.sourceWidth = PI(p, sourceWidth); q.sourceHeight = PI(p, sourceHeight); q.fpsNum = PU(p, fpsNum); q.fpsDenom = PU(p, fpsDenom);
     q.bframes = PI(p, bframes); q.keyframeMax = PI(p, keyframeMax); q.maxNumReferences = PI(p, maxNumReferences);
-    q.scenecutThreshold = PI(p, scenecutThreshold); q.lookaheadDepth = PI(p, lookaheadDepth); q.keyframeMin = PI(p, keyframeMin); q.bFrameAdaptive = PI(p, bFrameAdaptive); q.bOpenGOP = PI(p, bOpenGOP) != 0; q.bBPyramid = PI(p, bBPyramid) != 0; q.lookaheadSlices = PI(p, lookaheadSlices); q.bEnableWeightedPred = PI(p, bEnableWeightedPred) != 0; q.bEnableWeightedBiPred = PI(p, bEnableWeightedBiPred) != 0;
+    q.scenecutThreshold = PI(p, scenecutThreshold); q.bHistBasedSceneCut = PI(p, bHistBasedSceneCut) != 0; q.lookaheadDepth = PI(p, lookaheadDepth); q.keyframeMin = PI(p, keyframeMin); q.bFrameAdaptive = PI(p, bFrameAdaptive); q.bOpenGOP = PI(p, bOpenGOP) != 0; q.bBPyramid = PI(p, bBPyramid) != 0; q.lookaheadSlices = PI(p, lookaheadSlices); q.bEnableWeightedPred = PI(p, bEnableWeightedPred) != 0; q.bEnableWeightedBiPred = PI(p, bEnableWeightedBiPred) != 0;
     q.qp = PI(p, rc_qp); q.ipFactor = PD(p, rc_ipFactor); q.pbFactor = PD(p, rc_pbFactor);
     q.rateControlMode = PI(p, rc_rateControlMode); q.rfConstant = PD(p, rc_rfConstant); q.qCompress = PD(p, rc_qCompress); q.qgSize = PI(p, rc_qgSize);
     q.aqMode = PI(p, rc_aqMode); q.aqStrength = PD(p, rc_aqStrength); q.cuTree = PI(p, rc_cuTree) != 0;

@@ -22,9 +22,34 @@ set -euo pipefail
 REF=${X265_REFERENCE:-/root/reference}
 HERE=$(cd "$(dirname "$0")" && pwd)
 OUT=$HERE/_ref
-if [ ! -d "$REF/source" ]; then
-    echo "build_ref.sh: $REF/source not present (GPU box?) -- keeping prebuilt oracle/_ref as is" >&2
-    exit 0
+# X265_REF_DRIVER_OUT: where librefprimsD.so goes (default: oracle/_ref); X265_REF_DRIVER_ONLY=1: build nothing but that driver, on the objects oracle/_ref already has
+DRV=${X265_REF_DRIVER_OUT:-$OUT}
+if [ ! -d "$REF/source" ] || [ -n "${X265_REF_DRIVER_ONLY:-}" ]; then
+    # No reference sources (or only the driver is wanted).  A prebuilt oracle/_ref that still has the reference's objects and headers is enough to build OUR driver (oracle/refprims.cpp) again, so that
+    # an entry point added to it since the prebuilt copy was made is there; anything else is kept as it is
+    if [ -d "$OUT/include/common" ] && [ -d "$OUT/cfg" ] && ls "$OUT"/obj8/common_*.o "$OUT"/obj10/common_*.o >/dev/null 2>&1; then
+        INC=$OUT/include
+        if ! (
+        mkdir -p "$DRV" || exit 1
+        for D in 8 10; do
+            HBD=0; [ "$D" != 8 ] && HBD=1
+            g++ -O2 -std=gnu++11 -fPIC -ffast-math -mstackrealign -fno-exceptions -w -DX265_ARCH_X86=1 -DX86_64=1 -DHAVE_INT_TYPES_H=1 -D__STDC_LIMIT_MACROS=1 \
+                -DHIGH_BIT_DEPTH=$HBD -DX265_DEPTH=$D -DEXPORT_C_API=1 -DX265_NS=x265 -DHAVE_STRTOK_R=1 -DX265_VERSION=prebuilt -I"$OUT/cfg" -I"$INC" -I"$INC/common" -I"$INC/encoder" \
+                -shared -o "$DRV/librefprims$D.so.tmp" "$HERE/refprims.cpp" "$OUT"/obj$D/common_*.o "$OUT"/obj$D/encoder_*.o -lpthread -ldl || exit 1
+            mv -f "$DRV/librefprims$D.so.tmp" "$DRV/librefprims$D.so" || exit 1
+        done ); then
+            # (a prebuilt copy that cannot be written to: the tests that need a newer driver build it into a directory of their own, tests/hevc_testlib.py: load_ref_with)
+            echo "build_ref.sh: could not build oracle/refprims.cpp again into $DRV -- keeping prebuilt oracle/_ref as is" >&2
+            if [ -n "${X265_REF_DRIVER_ONLY:-}" ]; then exit 1; fi
+            exit 0
+        fi
+        echo "build_ref.sh: oracle/refprims.cpp built again on the prebuilt objects of oracle/_ref into $DRV" >&2
+        exit 0
+    elif [ ! -d "$REF/source" ]; then
+        echo "build_ref.sh: $REF/source not present (GPU box?) -- keeping prebuilt oracle/_ref as is" >&2
+        exit 0
+    fi
+    # (only the driver is wanted, oracle/_ref has no objects, the sources are there: the whole build below)
 fi
 mkdir -p "$OUT"
 SRC=$REF/source
@@ -64,7 +89,8 @@ build_depth() {
     g++ -shared -o "$OUT/libx265_ref$D.so" $objs -lpthread -ldl
     g++ -o "$OUT/x265_ref$D" $cliobjs $objs -lpthread -ldl
     # C-ABI driver around the reference primitive table (our file, includes reference headers at compile time)
-    g++ $FLAGS -shared -o "$OUT/librefprims$D.so" "$HERE/refprims.cpp" $objs -lpthread -ldl
+    mkdir -p "$DRV"
+    g++ $FLAGS -shared -o "$DRV/librefprims$D.so" "$HERE/refprims.cpp" $objs -lpthread -ldl
     # the reference encoder as a program whose primitive table can be overridden through the drop-in hook (our file + reference objects)
     g++ $FLAGS -o "$OUT/x265_dropin$D" "$HERE/ref_encode_with_table.cpp" $objs -lpthread -ldl
     # a libx265 client that fills x265_param with the reference's own functions and encodes through ANOTHER library's x265_api table (our file + reference objects)

@@ -1791,6 +1791,143 @@ int ref_lowres_frame_cost(const pixel* const* luma, intptr_t stride, int width, 
     return ncu;
 }
 
+/* ---- lookahead frame cost, the paths estimateFrameCost does not take on a small picture without a thread pool: the reference's own CostEstimateGroup::estimateCUCost
+ * (slicetype.cpp:4077-4249) driven block by block on the same fixture as above, with
+ *  - cooperative slices looped as processTasks does (slicetype.cpp:3957-3968): slice i = block rows [i rowsPerSlice, (i + 1) rowsPerSlice), the last slice to the bottom, lastRow
+ *    on each slice's bottom row, slice = i (the slices share nothing, so one after the other equals the threaded run); numSlices <= 1: the loop of :4050-4059, slice = -1;
+ *  - the caller's bDoSearch[2] (estimateFrameCost would pick its own, :3987-3988); a list that is not searched has its field and MV costs copied in from mvs / mvCosts first;
+ *  - weight[0] != 0: fenc->weightedRef[b - p0] set up as LookaheadTLD::weightsAnalyse does once it has chosen (scale, denom, offset) = weight[1..3] (:893-902, :966-978):
+ *    weight_pp over all four padded buffers of p0, isWeighted = true (estimateFrameCost would clear it, :3997).
+ * mvs i16[2][ncu][2] and mvCosts i32[2][ncu] are in / out; sliceSums i64[max(numSlices, 1)][2] = m_slice[i].costEst, .intraMbs (unsliced: the picture's own costEst before
+ * the B scaling and intraMbs[b - p0]). ---- */
+namespace {
+struct PathsGroup : public CostEstimateGroup
+{
+    PathsGroup(Lookahead& l, Lowres** f) : CostEstimateGroup(l, f) {}
+    void run(LookaheadTLD& tld, int p0, int p1, int b, bool bDoSearch[2], int numSlices, int rowsPerSlice)
+    {
+        Lowres* fenc = m_frames[b];
+        const int wcu = m_lookahead.m_8x8Width, hcu = m_lookahead.m_8x8Height;
+        fenc->costEst[b - p0][p1 - b] = 0; fenc->costEstAq[b - p0][p1 - b] = 0; fenc->intraMbs[b - p0] = 0;
+        memset(&m_slice, 0, sizeof(m_slice));
+        if (numSlices > 1)
+        {
+            for (int i = 0; i < numSlices; i++)
+            {
+                const int firstY = rowsPerSlice * i, lastY = (i == numSlices - 1) ? hcu - 1 : rowsPerSlice * (i + 1) - 1;
+                bool lastRow = true;
+                for (int cuY = lastY; cuY >= firstY; cuY--)
+                {
+                    fenc->rowSatds[b - p0][p1 - b][cuY] = 0;
+                    for (int cuX = wcu - 1; cuX >= 0; cuX--) estimateCUCost(tld, cuX, cuY, p0, p1, b, bDoSearch, lastRow, i, 0);
+                    lastRow = false;
+                }
+            }
+        }
+        else
+        {
+            bool lastRow = true;
+            for (int cuY = hcu - 1; cuY >= 0; cuY--)
+            {
+                fenc->rowSatds[b - p0][p1 - b][cuY] = 0;
+                for (int cuX = wcu - 1; cuX >= 0; cuX--) estimateCUCost(tld, cuX, cuY, p0, p1, b, bDoSearch, lastRow, -1, 0);
+                lastRow = false;
+            }
+        }
+    }
+};
+}
+int ref_lowres_frame_cost_paths(const pixel* const* luma, intptr_t stride, int width, int height, int marginX, int marginY, int p0, int b, int p1, int bframes,
+                                int numSlices, int rowsPerSlice, const int32_t* doSearch, const int32_t* weight,
+                                uint16_t* lowresCosts, int16_t* mvs, int32_t* mvCosts, int32_t* intraCost, int32_t* rowSatds, int64_t* sliceSums)
+{
+    ensure();
+    if (numSlices > CostEstimateGroup::MAX_COOP_SLICES || b <= p0 || p1 < b) return -1;
+    x265_param* param = x265_param_alloc();
+    x265_param_default(param);
+    param->sourceWidth = width; param->sourceHeight = height; param->internalCsp = X265_CSP_I420; param->bframes = bframes;
+    param->bEnableWeightedPred = 0; param->bEnableWeightedBiPred = 0; param->rc.aqMode = 0; param->rc.cuTree = 0; param->lookaheadSlices = 0; param->bEnableHME = 0;
+    param->maxSlices = 1; param->bFrameBias = 0; param->rc.qgSize = 32; param->bEnableTemporalFilter = 0;
+    Lookahead* la = new Lookahead(param, NULL);
+    Lowres* frames[3];
+    PicYuv* pics[3];
+    for (int k = 0; k < 3; k++)
+    {
+        pics[k] = new PicYuv;
+        pics[k]->m_param = param; pics[k]->m_picWidth = width; pics[k]->m_picHeight = height; pics[k]->m_lumaMarginX = marginX; pics[k]->m_lumaMarginY = marginY;
+        pics[k]->m_stride = stride; pics[k]->m_picOrg[0] = const_cast<pixel*>(luma[k]);
+        frames[k] = new Lowres();
+        if (!frames[k]->create(param, pics[k], param->rc.qgSize)) return -1;
+        frames[k]->init(pics[k], k);
+    }
+    const int wcu = la->m_8x8Width, hcu = la->m_8x8Height, ncu = wcu * hcu;
+    LookaheadTLD* tld = new LookaheadTLD;
+    tld->init(wcu, hcu, ncu);
+    for (int k = 0; k < 3; k++) tld->lowresIntraEstimate(*frames[k], param->rc.qgSize);
+    Lowres* f = frames[b];
+    Lowres* ref = frames[p0];
+    const bool bidir = p1 > b;
+    bool bDoSearch[2] = { doSearch[0] != 0, bidir && doSearch[1] != 0 };
+    for (int l = 0; l < 1 + (int)bidir; l++)
+    {
+        if (bDoSearch[l]) continue;
+        const int dist = l ? p1 - b : b - p0;
+        for (int i = 0; i < ncu; i++)
+        {
+            f->lowresMvs[l][dist][i].x = mvs[(l * ncu + i) * 2]; f->lowresMvs[l][dist][i].y = mvs[(l * ncu + i) * 2 + 1];
+            f->lowresMvCosts[l][dist][i] = mvCosts[l * ncu + i];
+        }
+    }
+    pixel* wbuffer = NULL;
+    if (weight && weight[0])
+    {
+        /* weightsAnalyse, slicetype.cpp:893-902 and :966-978 (allocWeightedRef :861-877) */
+        const intptr_t planesize = ref->buffer[1] - ref->buffer[0];
+        const int paddedLines = (int)(planesize / f->lumaStride);
+        wbuffer = X265_MALLOC(pixel, 4 * planesize);
+        ReferencePlanes& weightedRef = f->weightedRef[b - p0];
+        const intptr_t padoffset = f->lowresPlane[0] - f->buffer[0];
+        for (int i = 0; i < 4; i++) weightedRef.lowresPlane[i] = wbuffer + i * planesize + padoffset;
+        weightedRef.fpelPlane[0] = weightedRef.lowresPlane[0];
+        weightedRef.lumaStride = f->lumaStride;
+        weightedRef.isLowres = true;
+        weightedRef.isHMELowres = ref->bEnableHME;
+        const int scale = weight[1], denom = weight[2], offset = weight[3] << (X265_DEPTH - 8);
+        const int round = denom ? 1 << (denom - 1) : 0;
+        const int correction = IF_INTERNAL_PREC - X265_DEPTH;
+        const intptr_t rstride = ref->lumaStride;
+        for (int i = 0; i < 4; i++)
+            g_p.weight_pp(ref->buffer[i], wbuffer + i * planesize, rstride, (int)rstride, paddedLines, scale, round << correction, denom + correction, offset);
+        weightedRef.isWeighted = true;
+    }
+    else
+        f->weightedRef[b - p0].isWeighted = false;
+    PathsGroup g(*la, frames);
+    g.run(*tld, p0, p1, b, bDoSearch, numSlices, rowsPerSlice);
+    memcpy(lowresCosts, f->lowresCosts[b - p0][p1 - b], sizeof(uint16_t) * ncu);
+    for (int l = 0; l < 2; l++)
+    {
+        const int dist = l ? p1 - b : b - p0;
+        const bool have = l ? bidir : true;
+        for (int i = 0; i < ncu; i++)
+        {
+            mvs[(l * ncu + i) * 2] = have ? f->lowresMvs[l][dist][i].x : 0; mvs[(l * ncu + i) * 2 + 1] = have ? f->lowresMvs[l][dist][i].y : 0;
+            mvCosts[l * ncu + i] = have ? f->lowresMvCosts[l][dist][i] : 0;
+        }
+    }
+    memcpy(intraCost, f->intraCost, sizeof(int32_t) * ncu);
+    memcpy(rowSatds, f->rowSatds[b - p0][p1 - b], sizeof(int32_t) * hcu);
+    if (numSlices > 1)
+        for (int i = 0; i < numSlices; i++) { sliceSums[2 * i] = g.m_slice[i].costEst; sliceSums[2 * i + 1] = g.m_slice[i].intraMbs; }
+    else
+    { sliceSums[0] = f->costEst[b - p0][p1 - b]; sliceSums[1] = f->intraMbs[b - p0]; }
+    f->weightedRef[b - p0].isWeighted = false;
+    X265_FREE(wbuffer);
+    for (int k = 0; k < 3; k++) { frames[k]->destroy(param); delete frames[k]; pics[k]->m_picOrg[0] = NULL; }
+    delete tld;
+    return ncu;
+}
+
 /* ---- adaptive quantisation, block energies: the reference's own LookaheadTLD::acEnergyCu over a picture (slicetype.cpp:264-283) ---- */
 int ref_aq_energy(const pixel* y, const pixel* u, const pixel* v, intptr_t stride, intptr_t cstride, int width, int height, int qgSize, uint32_t* energy, uint64_t* wp)
 {

@@ -115,6 +115,31 @@ def load_ref(depth):
     return PrimLib(ref_path(depth), "ref_", depth)
 
 
+_REF_DRIVER_DIR = None
+
+
+def load_ref_with(depth, name):
+    """load_ref whose driver has the entry ref_<name>.  oracle/_ref/librefprims*.so is OUR file (oracle/refprims.cpp) linked to the reference's objects; a copy of oracle/_ref
+    made before the entry was added lacks it, and then the driver alone is built again from the objects and headers oracle/_ref keeps (oracle/build_ref.sh), into a
+    directory of this process"""
+    global _REF_DRIVER_DIR
+    R = load_ref(depth)
+    if R.has(name):
+        return R
+    if _REF_DRIVER_DIR is None:
+        import subprocess
+        import tempfile
+        import atexit
+        import shutil
+        d = tempfile.mkdtemp(prefix="refprims_")
+        atexit.register(shutil.rmtree, d, True)
+        subprocess.check_call(["bash", os.path.join(ORACLE_DIR, "build_ref.sh")], env=dict(os.environ, X265_REF_DRIVER_ONLY="1", X265_REF_DRIVER_OUT=d))
+        _REF_DRIVER_DIR = d
+    R = PrimLib(os.path.join(_REF_DRIVER_DIR, "librefprims%d.so" % depth), "ref_", depth)
+    assert R.has(name), "oracle/_ref has no ref_%s and the driver could not be built again on its objects" % name
+    return R
+
+
 def hip_path(depth):
     return os.path.join(PKG_DIR, "lib", "libx265amd_main.so" if depth == 8 else "libx265amd_main10.so")
 
@@ -3998,8 +4023,9 @@ def lowres_cost_sums(c, lowres_costs, bcost, bidir):
 
 
 def lowres_cost_run_hip(L, me, c, p0, b, p1):
-    """Lowres::init of the three frames, intra costs, then the frame cost of b against p0 (and p1 when p1 > b) -- a P cost first when the L0 MVs
-    of that distance are needed, exactly as the reference's estimateFrameCost finds them"""
+    """Lowres::init of the three frames, intra costs, then ONE frame cost of b against p0 (and p1 when p1 > b) through x265amd_lowres_frame_cost, unsliced and unweighted, with
+    every list searched (do_search0 = 1, do_search1 = bidir): what estimateFrameCost does on fresh Lowres objects.  No field is reused here; the reuse, sliced and weighted
+    forms are LowresPathsDev's (below)"""
     import torch
     depth = c["depth"]
     dt = c["lumas"][0].dtype
@@ -4038,6 +4064,377 @@ def lowres_cost_run_hip(L, me, c, p0, b, p1):
     mvs = np.stack([d_mvs[l].cpu().numpy().reshape(ncu, 2) for l in range(2)]); mvc = np.stack([d_mvc[l].cpu().numpy() for l in range(2)])
     score, est, intra_mbs, rows_ = lowres_cost_sums(c, lc, bc, bidir)
     return dict(lowres_costs=lc, mvs=mvs, mv_costs=mvc, intra_cost=intra[b].cpu().numpy(), row_satds=rows_, sums=np.array([score, est, intra_mbs], np.int64))
+
+
+# ---- lookahead frame cost, the paths beside the plain one: cooperative slices, weighted search planes, reused motion fields (tests/test_lookahead_paths.py) ----
+# golden: tests/golden/lowres_paths_golden.npz, made by tests/golden/make_lowres_paths_golden.py from the reference's own estimateCUCost (oracle/refprims.cpp:
+# ref_lowres_frame_cost_paths)
+PATHS_GOLD = os.path.join(GOLDEN_DIR, "lowres_paths_golden.npz")
+PATHS_WEIGHT = (90, 7, 10)          # (scale, log2 denom, offset at 8 bits): 90 / 128 = 0.70, the fade of lowres_fade_case
+# scene -> (bit depth, seed, crop, fade).  s8 / s10 are scenes of tests/test_lowres.py's COST_CASES, so their unsliced entries must repeat lowres_cost_golden.npz
+PATHS_SCENES = {"s8": (8, 22, (0, 0), False), "c8": (8, 23, (24, 40), False), "f8": (8, 26, (0, 0), True),
+                "s10": (10, 24, (0, 0), False), "c10": (10, 25, (24, 40), False), "f10": (10, 27, (0, 0), True)}
+# slice layouts the reference can form (numSlices = hcu / rowsPerSlice), per block-row count; the last one is "one slice" = no slices
+PATHS_LAYOUTS = {12: [(4, 3), (5, 2), (6, 2), (12, 1)], 10: [(5, 2), (3, 3), (10, 1)]}
+PATHS_KINDS = {"P": (0, 1, 1), "B": (0, 1, 2)}
+LOWRES_JOB_DT = np.dtype([("d_fenc", "<u8"), ("d_ref0", "<u8", 4), ("d_ref1", "<u8", 4), ("d_intra_cost", "<u8"), ("d_mvs0", "<u8"), ("d_mv_costs0", "<u8"), ("d_mvs1", "<u8"),
+                          ("d_mv_costs1", "<u8"), ("d_lowres_costs", "<u8"), ("d_bcost", "<u8"), ("do_search0", "<i4"), ("do_search1", "<i4"), ("rows_per_slice", "<i4"),
+                          ("num_slices", "<i4"), ("d_ref0w", "<u8", 4)])         # x265amd_lowres_cost_job (include/x265amd.h)
+
+
+def lowres_fade_case(depth, seed, crop=(0, 0)):
+    """lowres_cost_case under a fade: frame 1 is its own content (frame 0's plus the scene's motion) at 179 / 256 = 0.70 of the brightness plus 10, frame 2 at 102 / 256 = 0.40
+    plus 20 -- so the weight (90, 7, 10) on frame 0 predicts frame 1 far better than no weight, and the plain average of frames 0 and 2 predicts it as well (0.70, +10)"""
+    c = lowres_cost_case(depth, seed, crop)
+    sh = depth - 8
+    for k, (num, off) in ((1, (179, 10)), (2, (102, 20))):
+        l = c["lumas"][k]
+        c["lumas"][k] = np.ascontiguousarray((((l.astype(np.int64) * num + 128) >> 8) + (off << sh)).astype(l.dtype))
+    return c
+
+
+def lowres_paths_scene(scene):
+    depth, seed, crop, fade = PATHS_SCENES[scene]
+    return (lowres_fade_case if fade else lowres_cost_case)(depth, seed, crop)
+
+
+def lowres_paths_specs():
+    """every entry of the golden, in the order in which the reference computed them: name -> dict(scene, kind, slices (rowsPerSlice, numSlices) or (0, 0), search (list 0,
+    list 1), weight or None, src: the entry whose fields the lists that are not searched read)"""
+    specs = {}
+
+    def add(name, scene, kind, slices=(0, 0), search=None, weight=None, src=None):
+        specs[name] = dict(scene=scene, kind=kind, slices=slices, search=search or (1, int(kind == "B")), weight=weight, src=src)
+
+    for depth in (8, 10):
+        s, cr, f = "s%d" % depth, "c%d" % depth, "f%d" % depth
+        for scene, hcu in ((s, 12), (cr, 10)):
+            for kind in ("P", "B"):
+                add("%s/%s/u" % (scene, kind), scene, kind)
+                for (rps, ns) in PATHS_LAYOUTS[hcu]:
+                    add("%s/%s/%dx%d" % (scene, kind, rps, ns), scene, kind, (rps, ns))
+        lay = (4, 3) if depth == 8 else (5, 2)
+        add(f + "/P/u", f, "P")
+        for kind in ("P", "B"):
+            add("%s/%s/w" % (f, kind), f, kind, weight=PATHS_WEIGHT)
+            add("%s/%s/w%dx%d" % (f, kind, lay[0], lay[1]), f, kind, lay, weight=PATHS_WEIGHT)
+        # reuse: the searched P estimate's list-0 field read by a B estimate that searches list 1 only, then that B estimate measured again with both fields read
+        add(s + "/B/mixed", s, "B", search=(0, 1), src=s + "/P/u")
+        add(s + "/B/measure", s, "B", search=(0, 0), src=s + "/B/mixed")
+        add("%s/B/mixed%dx%d" % (s, lay[0], lay[1]), s, "B", lay, search=(0, 1), src="%s/P/%dx%d" % (s, lay[0], lay[1]))
+        # and as the reference runs a fade: the P estimate searched list 0 on the weighted planes; the B estimate that reads that field has no weight (estimateFrameCost
+        # clears isWeighted and analyses weights only when it searches list 0, slicetype.cpp:3997-3999).  A search of list 0 here would find other vectors
+        add(f + "/B/reuse", f, "B", search=(0, 1), src=f + "/P/w")
+    return specs
+
+
+def lowres_paths_run_ref(R, c, spec, src=None):
+    """one entry from the reference (CPU, oracle/_ref): src = the result whose fields are read"""
+    p0, b, p1 = PATHS_KINDS[spec["kind"]]
+    isz = c["lumas"][0].itemsize
+    ptrs = (C.c_void_p * 3)(*[l.ctypes.data + (MC_MY * c["stride"] + MC_MX) * isz for l in c["lumas"]])
+    ncu = c["wcu"] * c["hcu"]
+    rps, ns = spec["slices"]
+    lc = np.zeros(ncu, np.uint16); ic = np.zeros(ncu, np.int32); rows = np.zeros(c["hcu"], np.int32); ssum = np.zeros((max(ns, 1), 2), np.int64)
+    mvs = src["mvs"].copy() if src is not None else np.zeros((2, ncu, 2), np.int16)
+    mvc = src["mv_costs"].copy() if src is not None else np.zeros((2, ncu), np.int32)
+    search = np.array(spec["search"], np.int32)
+    weight = np.array((1,) + tuple(spec["weight"]) if spec["weight"] else (0, 0, 0, 0), np.int32)
+    R.lib.ref_lowres_frame_cost_paths.restype = C.c_int
+    n = R.lib.ref_lowres_frame_cost_paths(ptrs, C.c_int64(c["stride"]), c["W"], c["H"], MC_MX, MC_MY, p0, b, p1, 2, ns, rps, _ptr(search), _ptr(weight),
+                                          _ptr(lc), _ptr(mvs), _ptr(mvc), _ptr(ic), _ptr(rows), _ptr(ssum))
+    assert n == ncu, (n, ncu)
+    return dict(lowres_costs=lc, mvs=mvs, mv_costs=mvc, intra_cost=ic, row_satds=rows, slice_sums=ssum)
+
+
+def lowres_paths_golden_entry(g, name):
+    return {k: g["%s/%s" % (name, k)] for k in ("lowres_costs", "mvs", "mv_costs", "row_satds", "slice_sums")}
+
+
+def lowres_slice_rows(hcu, slices):
+    """block rows [first, last] of every slice (processTasks, slicetype.cpp:3957-3958); no slices: the picture"""
+    rps, ns = slices
+    if ns <= 1:
+        return [(0, hcu - 1)]
+    return [(rps * i, hcu - 1 if i == ns - 1 else rps * (i + 1) - 1) for i in range(ns)]
+
+
+def lowres_slice_sums(c, lowres_costs, bcost, bidir, slices):
+    """lowres_cost_sums per slice: estimateCUCost's tail (slicetype.cpp:4220-4245) adds a block that is not on the PICTURE's edge to its slice's costEst / intraMbs"""
+    wcu, hcu = c["wcu"], c["hcu"]
+    bc = bcost.reshape(hcu, wcu).astype(np.int64)
+    inner = np.zeros((hcu, wcu), bool)
+    inner[1:hcu - 1, 1:wcu - 1] = True
+    if wcu <= 2 or hcu <= 2:
+        inner[:] = True
+    intra = ((lowres_costs.reshape(hcu, wcu) >> 14) == 0) & inner
+    out = []
+    for (y0, y1) in lowres_slice_rows(hcu, slices):
+        out.append((int(bc[y0:y1 + 1][inner[y0:y1 + 1]].sum()), 0 if bidir else int(intra[y0:y1 + 1].sum())))
+    return np.array(out, np.int64)
+
+
+class LowresPathsDev:
+    """the device side of a lowres_cost_case: per frame ONE buffer of the four padded lowres planes (as Lowres::create lays them out) and the intra costs; estimates in any of
+    the forms of x265amd_lowres_cost_job go through x265amd_lowres_frame_cost_batch, any number per launch"""
+
+    def __init__(self, L, me, c):
+        import torch
+        self.torch, self.L, self.me, self.c = torch, L, me, c
+        depth = c["depth"]
+        self.dt = c["lumas"][0].dtype
+        isz = self.isz = self.dt.itemsize
+        lw, lh = c["wcu"] * 8, c["hcu"] * 8
+        lstride = (c["W"] // 2) + 2 * MC_MX
+        lstride += (32 - (lstride & 31)) & 31
+        self.lstride, self.rows = lstride, lh + 2 * MC_MY
+        self.planesize = self.rows * lstride                     # samples
+        self.o = (MC_MY * lstride + MC_MX) * isz
+        self.ncu = c["wcu"] * c["hcu"]
+        self.buf, self.intra = [], []
+        for k in range(3):
+            d_src = torch.from_numpy(c["lumas"][k].view(np.uint8)).cuda()
+            d_buf = torch.zeros(4 * self.planesize * isz, dtype=torch.uint8, device="cuda")
+            ptrs = (C.c_void_p * 4)(*self.plane_ptrs(d_buf))
+            assert L.lib.x265amd_lowres_init(None, C.c_void_p(d_src.data_ptr() + (MC_MY * c["stride"] + MC_MX) * isz), C.c_int64(c["stride"]), lw, lh, ptrs, C.c_int64(lstride),
+                                             MC_MX, MC_MY) == 0
+            d_cost = torch.zeros(self.ncu, dtype=torch.int32, device="cuda"); d_mode = torch.zeros(self.ncu, dtype=torch.uint8, device="cuda")
+            assert L.lib.x265amd_lowres_intra_costs(None, C.c_void_p(d_buf.data_ptr() + self.o), C.c_int64(lstride), c["wcu"], c["hcu"], LOWRES_LAMBDA[depth],
+                                                    C.c_void_p(d_cost.data_ptr()), C.c_void_p(d_mode.data_ptr())) == 0
+            self.buf.append(d_buf); self.intra.append(d_cost)
+        torch.cuda.synchronize()
+        self.wbuf = {}
+
+    def plane_ptrs(self, d_buf):
+        """sample (0, 0) of the four planes of a buffer"""
+        return [d_buf.data_ptr() + k * self.planesize * self.isz + self.o for k in range(4)]
+
+    def weighted(self, k, weight):
+        """LookaheadTLD::weightsAnalyse's weighted copies of frame k's four planes: x265amd_weight_buffer over the whole buffer, margins included"""
+        key = (k,) + tuple(weight)
+        if key not in self.wbuf:
+            scale, denom, off = weight
+            corr = 14 - self.c["depth"]
+            d = self.torch.zeros_like(self.buf[k])
+            assert self.L.lib.x265amd_weight_buffer(None, C.c_void_p(self.buf[k].data_ptr()), C.c_void_p(d.data_ptr()), C.c_size_t(4 * self.planesize), scale,
+                                                    (1 << (denom - 1) if denom else 0) << corr, denom + corr, off << (self.c["depth"] - 8)) == 0, self.L.lib.x265amd_last_error()
+            self.torch.cuda.synchronize()
+            self.wbuf[key] = d
+        return self.wbuf[key]
+
+    def host_planes(self, d_buf):
+        return d_buf.cpu().numpy().view(self.dt).reshape(4 * self.rows, self.lstride)
+
+    def run(self, jobs):
+        """jobs: dicts(kind, slices, search, weight, src = the result whose fields the lists that are not searched read) -> results in one launch.  Every output buffer starts
+        filled with a pattern that no result has; the fields that are only read are returned as they are AFTER the launch (mvs / mv_costs of that list)"""
+        torch = self.torch
+        ncu = self.ncu
+        rec = np.zeros(len(jobs), LOWRES_JOB_DT); keep = []
+        for i, j in enumerate(jobs):
+            p0, b, p1 = PATHS_KINDS[j["kind"]]
+            bidir = p1 > b
+            mv, mc = [], []
+            for l in range(2):
+                if not j["search"][l] and (l == 0 or bidir):
+                    mv.append(torch.from_numpy(j["src"]["mvs"][l].reshape(-1).copy()).cuda()); mc.append(torch.from_numpy(j["src"]["mv_costs"][l].copy()).cuda())
+                else:
+                    mv.append(torch.full((ncu * 2,), 0x5A5A, dtype=torch.int16, device="cuda")); mc.append(torch.full((ncu,), 0x5A5A5A5A, dtype=torch.int32, device="cuda"))
+            lc = torch.full((ncu,), 0x5A5A, dtype=torch.int16, device="cuda"); bc = torch.full((ncu,), 0x5A5A5A5A, dtype=torch.int32, device="cuda")
+            keep.append((mv, mc, lc, bc))
+            r = rec[i]
+            d = j.get("dev") or self                # (the pictures of another scene of the same size)
+            r["d_fenc"] = d.buf[b].data_ptr() + self.o
+            r["d_ref0"] = self.plane_ptrs(d.buf[p0])
+            if bidir:
+                r["d_ref1"] = self.plane_ptrs(d.buf[p1])
+                r["d_mvs1"], r["d_mv_costs1"], r["do_search1"] = mv[1].data_ptr(), mc[1].data_ptr(), int(j["search"][1])
+            r["d_intra_cost"] = d.intra[b].data_ptr()
+            r["d_mvs0"], r["d_mv_costs0"], r["do_search0"] = mv[0].data_ptr(), mc[0].data_ptr(), int(j["search"][0])
+            r["d_lowres_costs"], r["d_bcost"] = lc.data_ptr(), bc.data_ptr()
+            r["rows_per_slice"], r["num_slices"] = j["slices"]
+            if j.get("weight"):
+                r["d_ref0w"] = self.plane_ptrs(d.weighted(p0, j["weight"]))
+        torch.cuda.synchronize()
+        assert self.L.lib.x265amd_lowres_frame_cost_batch(None, self.me.ctx, rec.ctypes.data_as(C.c_void_p), len(jobs), C.c_int64(self.lstride), self.c["wcu"], self.c["hcu"]) == 0, \
+            self.L.lib.x265amd_last_error()
+        torch.cuda.synchronize()
+        sums = np.zeros(2 * len(jobs), np.int64)
+        assert self.L.lib.x265amd_lowres_cost_sums(None, rec.ctypes.data_as(C.c_void_p), len(jobs), self.c["wcu"], self.c["hcu"], sums.ctypes.data_as(C.c_void_p)) == 0
+        out = []
+        for i, (mv, mc, lc, bc) in enumerate(keep):
+            out.append(dict(lowres_costs=lc.cpu().numpy().view(np.uint16), bcost=bc.cpu().numpy(), mvs=np.stack([m.cpu().numpy().reshape(ncu, 2) for m in mv]),
+                            mv_costs=np.stack([m.cpu().numpy() for m in mc]), device_sums=(int(sums[2 * i]), int(sums[2 * i + 1]))))
+        return out
+
+
+def lowres_paths_assert(c, job, got, want, tag=""):
+    """one estimate of LowresPathsDev.run against its golden entry, bit for bit: lowresCosts, the row sums of the unclipped costs, the fields and MV costs of the lists the
+    estimate has, the per-slice sums (m_slice[i].costEst / intraMbs) and, over all slices, the device's own reduction"""
+    bidir = job["kind"] == "B"
+    assert np.array_equal(got["lowres_costs"], want["lowres_costs"]), (tag, "lowres_costs", np.argwhere(got["lowres_costs"] != want["lowres_costs"])[:6].ravel().tolist())
+    rows = got["bcost"].reshape(c["hcu"], c["wcu"]).astype(np.int64).sum(1)
+    assert np.array_equal(rows, want["row_satds"]), (tag, "row sums", rows.tolist(), want["row_satds"].tolist())
+    for l in range(1 + bidir):
+        assert np.array_equal(got["mvs"][l], want["mvs"][l]), (tag, "mvs", l, np.argwhere(got["mvs"][l] != want["mvs"][l])[:6].tolist())
+        assert np.array_equal(got["mv_costs"][l], want["mv_costs"][l]), (tag, "mv_costs", l, np.argwhere(got["mv_costs"][l] != want["mv_costs"][l])[:6].ravel().tolist())
+    ss = lowres_slice_sums(c, got["lowres_costs"], got["bcost"], bidir, job["slices"])
+    assert np.array_equal(ss, want["slice_sums"]), (tag, "slice sums", ss.tolist(), want["slice_sums"].tolist())
+    assert got["device_sums"] == (int(ss[:, 0].sum()), int(ss[:, 1].sum())), (tag, got["device_sums"], ss.tolist())
+
+
+# ---- weightCost with motion vectors, restated from the reference with the oracle's pieces (tests/test_lookahead_paths.py f, g) ----
+def weight_cand(depth, scale, denom, off):
+    """x265amd_weight_cand as weightCost passes weight_pp's arguments (weightPrediction.cpp:182-189)"""
+    corr = 14 - depth
+    return (1, scale, (1 << (denom - 1) if denom else 0) << corr, denom + corr, off << (depth - 8))
+
+
+WEIGHT_MARGIN = 32      # samples around the planes of the weight-cost fixtures: a clipped vector reaches 8 + 8 samples beyond the picture, an interpolation two more
+
+
+def weight_cost_planes(depth, seed, width, height, nplanes):
+    """source plane and nplanes reference planes (unrelated enough that reading the wrong one shows), each with WEIGHT_MARGIN samples around width x height"""
+    rng = np.random.default_rng(seed)
+    pmax = (1 << depth) - 1
+    dt = np.uint8 if depth == 8 else np.uint16
+    hh, ww = height + 2 * WEIGHT_MARGIN + 8, width + 2 * WEIGHT_MARGIN
+    ww += (32 - (ww & 31)) & 31
+    base = np.kron(rng.integers(0, pmax + 1, ((hh + 7) // 8, (ww + 7) // 8)), np.ones((8, 8), np.int64))[:hh, :ww]
+    refs = [np.clip(np.roll(base, (k, 2 * k), (0, 1)) + rng.integers(-24, 25, (hh, ww)) * (1 << (depth - 8)), 0, pmax).astype(dt) for k in range(nplanes)]
+    fenc = np.clip(base * 0.7 + (12 << (depth - 8)) + rng.integers(-6, 7, (hh, ww)) * (1 << (depth - 8)), 0, pmax).astype(dt)
+    return fenc, refs, ww
+
+
+def weight_cost_luma_mvs(seed, width, height):
+    """a field for mcLuma: every quarter-sample phase, vectors far outside the picture in the four directions, a zero vector"""
+    rng = np.random.default_rng(seed)
+    bw, bh = width >> 3, (height + 7) >> 3
+    mv = np.zeros((bh * bw, 2), np.int16)
+    for i in range(bh * bw):
+        ph = (i * 7) & 15
+        mv[i] = (4 * int(rng.integers(-5, 6)) + (ph & 3), 4 * int(rng.integers(-5, 6)) + (ph >> 2))
+        if (i + i // bw) % 3 == 1:
+            far = ((-3000, 5), (3000, -7), (6, -3000), (-9, 3000), (-2500, -2500), (2500, 2500))[(i // 3) % 6]
+            mv[i] = far
+    mv[0] = (0, 0)
+    return mv
+
+
+def mv_clip_luma(mv, x, y, width, height):
+    """mcLuma's clip to the picture + 8 samples (weightPrediction.cpp:72-73, :79-84)"""
+    return (min(max(int(mv[0]), (-x - 8) * 4), (width - x - 1 + 8) * 4), min(max(int(mv[1]), (-y - 8) * 4), (height - y - 1 + 8) * 4))
+
+
+def weight_cost_luma_expected(O, depth, fenc, refs, stride, width, height, mvs, intra, cand):
+    """weightAnalyse's luma measurement in the reference's order: mcLuma (weightPrediction.cpp:58-90: per 8x8 block the vector clipped, ReferencePlanes::lowresMC, lowres.h:71-96
+    -- the half-sample plane (y & 2) | ((x & 2) >> 1) at the full-sample offset, averaged by pixelavg_pp with the plane of the vector rounded up when it has a quarter part), then
+    weightCost (:169-218): weight_pp of the compensated plane, per block min(satd_8x8(reference, source), intra cost), summed in uint32 (intra None: the SATD alone, cache.intraCost
+    being what the caller hands in)"""
+    M = WEIGHT_MARGIN
+    tot = 0
+    cu = 0
+    for y in range(0, height, 8):
+        for x in range(0, width, 8):
+            def blk(plane, dx, dy):
+                return plane[M + y + dy:M + y + dy + 8, M + x + dx:M + x + dx + 8]
+            if mvs is None:
+                r = blk(refs[0], 0, 0).copy()
+            else:
+                qx, qy = mv_clip_luma(mvs[cu], x, y, width, height)
+                a = blk(refs[(qy & 2) | ((qx & 2) >> 1)], qx >> 2, qy >> 2).copy()
+                if (qx | qy) & 1:
+                    qx2, qy2 = qx + (qx & 1), qy + (qy & 1)
+                    b = blk(refs[(qy2 & 2) | ((qx2 & 2) >> 1)], qx2 >> 2, qy2 >> 2).copy()
+                    r = np.zeros((8, 8), a.dtype)
+                    O.lib.orc_pixelavg_pp(1, _ptr(r), C.c_int64(8), _ptr(a), C.c_int64(8), _ptr(b), C.c_int64(8))
+                else:
+                    r = a
+            if cand[0]:
+                w = np.zeros((8, 8), r.dtype)
+                O.lib.orc_weight_pp(_ptr(r), _ptr(w), C.c_int64(8), 8, 8, cand[1], cand[2], cand[3], cand[4])
+                r = w
+            v = O.call("satd", 1, r, 8, blk(fenc, 0, 0).copy(), 8)
+            tot += min(v, int(intra[cu])) if intra is not None else v
+            cu += 1
+    return tot & 0xFFFFFFFF
+
+
+def lowres_paths_compute_ref():
+    """every entry of lowres_paths_specs() from the reference (oracle/_ref), in the table's order: the arrays of lowres_paths_golden.npz"""
+    out, res, scenes = {}, {}, {}
+    for name, spec in lowres_paths_specs().items():
+        scene = spec["scene"]
+        if scene not in scenes:
+            scenes[scene] = lowres_paths_scene(scene)
+        c = scenes[scene]
+        r = lowres_paths_run_ref(load_ref_with(c["depth"], "lowres_frame_cost_paths"), c, spec, res[spec["src"]] if spec["src"] else None)
+        res[name] = r
+        for k in ("lowres_costs", "mvs", "mv_costs", "row_satds", "slice_sums"):
+            out["%s/%s" % (name, k)] = r[k]
+        if scene + "/intra_cost" not in out:
+            out[scene + "/intra_cost"] = r["intra_cost"]
+        assert np.array_equal(out[scene + "/intra_cost"], r["intra_cost"]), name
+    return out
+
+
+def chroma_weight_inside(x, y, low_cu_w, low_cu_h):
+    """mcChroma's condition (weightPrediction.cpp:121): the block's SAMPLE position against the lowres picture's size in blocks"""
+    return x < low_cu_w and y < low_cu_h
+
+
+def chroma_weight_mvs(seed, width, height, low_cu_w):
+    """a field as mcChroma indexes it (weightPrediction.cpp:114, :119, :123: mvs[y * lowresWidthInCU + block column], y the block's first sample row): every (x & 7, y & 7)
+    fraction class -- none, horizontal, vertical, both --, far vectors, a zero vector"""
+    rng = np.random.default_rng(seed)
+    n = height * low_cu_w + (width >> 3)
+    mv = np.stack([rng.integers(-40, 41, n), rng.integers(-40, 41, n)], 1).astype(np.int16)
+    mv[::5] = (mv[::5] >> 3) << 3                  # no fraction
+    mv[1::5, 1] = (mv[1::5, 1] >> 3) << 3          # horizontal only
+    mv[2::5, 0] = (mv[2::5, 0] >> 3) << 3          # vertical only
+    far = np.array([(-3000, 3), (3000, -5), (2, -3000), (-1, 3000)], np.int16)
+    for k in range(3, n, 7):
+        mv[k] = far[(k // 7) % 4]
+    mv[5] = (0, 0)
+    return mv
+
+
+def chroma_weight_cost_expected(O, depth, fenc, ref, stride, width, height, mvs, low_cu_w, low_cu_h, cand):
+    """weightAnalyse's chroma measurement (4:2:0) in the reference's order: mcChroma (weightPrediction.cpp:93-159) per 8x8 chroma block -- inside the lowres grid (:121) the vector
+    mvs[y * lowresWidthInCU + column] (<< 1, >> the chroma shifts: unchanged), clipped with the CHROMA plane's size (:116-117, :129-131), full-sample offset (mv >> 2), fraction
+    (mv & 7) through copy / filter_hpp / filter_vpp / filter_hps + filter_vsp; outside a copy --, then weightCost's chroma branch (:179-191, :213-215): weight_pp, satd_8x8"""
+    M = WEIGHT_MARGIN
+    dt = fenc.dtype
+    tot = 0
+    part = PU_SIZES.index((16, 16))             # chroma[csp].pu[LUMA_16x16]: 8x8 chroma samples at 4:2:0
+    for y in range(0, height, 8):
+        for bx, x in enumerate(range(0, width, 8)):
+            if mvs is not None and chroma_weight_inside(x, y, low_cu_w, low_cu_h):
+                mx, my = int(mvs[y * low_cu_w + bx][0]), int(mvs[y * low_cu_w + bx][1])
+                mx = min(max(mx, (-x - 8) * 4), (width - x - 1 + 8) * 4)
+                my = min(max(my, (-y - 8) * 4), (height - y - 1 + 8) * 4)
+                ty, tx = M + y + (my >> 2), M + x + (mx >> 2)
+                xf, yf = mx & 7, my & 7
+                p0 = C.c_void_p(ref.ctypes.data + (ty * stride + tx) * ref.itemsize)
+                r = np.zeros((8, 8), dt)
+                if not (xf | yf):
+                    r = ref[ty:ty + 8, tx:tx + 8].copy()
+                elif not yf:
+                    O.lib.orc_chroma_hpp(CSP_I420, part, p0, C.c_int64(stride), _ptr(r), C.c_int64(8), xf)
+                elif not xf:
+                    O.lib.orc_chroma_vpp(CSP_I420, part, p0, C.c_int64(stride), _ptr(r), C.c_int64(8), yf)
+                else:
+                    immed = np.zeros((8 + 3, 8), np.int16)
+                    O.lib.orc_chroma_hps(CSP_I420, part, p0, C.c_int64(stride), _ptr(immed), C.c_int64(8), xf, 1)
+                    O.lib.orc_chroma_vsp(CSP_I420, part, C.c_void_p(immed.ctypes.data + 8 * 2), C.c_int64(8), _ptr(r), C.c_int64(8), yf)
+            else:
+                r = ref[M + y:M + y + 8, M + x:M + x + 8].copy()
+            if cand[0]:
+                w = np.zeros((8, 8), dt)
+                O.lib.orc_weight_pp(_ptr(r), _ptr(w), C.c_int64(8), 8, 8, cand[1], cand[2], cand[3], cand[4])
+                r = w
+            tot += O.call("satd", 1, r, 8, fenc[M + y:M + y + 8, M + x:M + x + 8].copy(), 8)
+    return tot & 0xFFFFFFFF
 
 
 # ---- adaptive quantisation block energies (x265amd_aq_energy vs LookaheadTLD::acEnergyCu) ----

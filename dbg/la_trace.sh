@@ -1,10 +1,8 @@
-# the lookahead's batch kernels beside the first pictures (hold 0) and alone (hold 1: every decision before the first picture starts): rocprofv3 kernel trace, 2160p
-cd /tmp && export TMPDIR=/tmp
-cd $GRAFT_REPO_ROOT
-for hold in 0 1; do
-  X265AMD_HOLD_UNTIL_FLUSH=$hold X265AMD_TIMING=1 rocprofv3 --kernel-trace -d gpurun_out/la$hold -o la -- python3 dbg/enc_cfg.py 3840x2160 medium 8 20 ${WARM:-0} 2> gpurun_out/la_err_$hold.txt | tail -1
-  grep "decision:\|lookahead:" gpurun_out/la_err_$hold.txt | head -4
-  python3 - gpurun_out/la$hold/la_results.db <<'PY'
+# the lookahead's batch kernels beside the first pictures: rocprofv3 kernel trace, 2160p: dbg/la_trace.sh <outdir>   (from the repository's root)
+out=$1; mkdir -p $out
+X265AMD_TIMING=1 rocprofv3 --kernel-trace -d $out/la -o la -- python3 dbg/enc_cfg.py 3840x2160 medium 8 20 ${WARM:-0} 2> $out/la_err.txt | tail -1
+grep "decision:\|lookahead:" $out/la_err.txt | head -4
+python3 - $out/la/la_results.db <<'PY'
 import sqlite3, sys
 db = sqlite3.connect(sys.argv[1])
 cols = [r[1] for r in db.execute("pragma table_info(kernels)")]
@@ -15,4 +13,3 @@ for r in rows:
     if "lowres_cost" in r[ni] or "job_server" in r[ni]:
         print("  %-24s start %8.1f ms dur %8.2f ms grid %s x %s" % (r[ni][:24], (r[si] - t0) / 1e6, (r[ei] - r[si]) / 1e6, r[gx], r[gy]))
 PY
-done

@@ -4692,7 +4692,7 @@ def filter_schedule(kind, seed, ctuW, ctuH, max_step=None):
 
 
 def filter_min_chunks(m, ctuW):
-    """(min_chunk, min_chunk_last) of filterRowsCols for the three values a chunk minimum can take: 1 (X265AMD_FILTER_CHUNK=1), 2 (P pictures: 1 in the last three
+    """(min_chunk, min_chunk_last) of filterRowsCols for three values of the chunk minimum: 1 (the planner's smallest; the encoder does not use it), 2 (P pictures: 1 in the last three
     rows), 'w' (B pictures: whole rows)"""
     return {1: (1, 1), 2: (2, 1), "w": (ctuW, ctuW)}[m]
 

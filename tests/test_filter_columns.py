@@ -16,8 +16,8 @@ column xMax of the CTU rows of lines yMin .. yMax (clamped into the picture) onc
 block that lies in the left margin alone (xMax < 0) waits for nothing there, but its CTU only starts behind gateCtuReady, which has seen every row it can reach
 published beyond column 0.
 
-Records and SAO parameters are passed as device memory here (the encoder's X265AMD_DEBLOCK_UNITS_COPY=1 / X265AMD_SAO_PARAMS_COPY=1 form); the default form,
-mapped host memory the kernels read in place, stays covered by the stream fixtures only (tests/test_encoder_api.py, test_encoder_full_size.py).
+Records and SAO parameters are passed as device memory here (the C entry points take either; the encoder itself once had this copy form behind two switches); the
+encoder's form, mapped memory the kernels read in place, stays covered by the stream fixtures only (tests/test_encoder_api.py, test_encoder_full_size.py).
 
 What these tests were seen to catch (value-only changes on a scratch copy, 8-bit library, one run each):
   - a chunk's seam edge nobody's (x265amd_deblock_rows_cols: xvEnd = 16 * ctu_col_end): test_filter_columns_product, 200x72 wavefront schedule, chunk minimum 1, sweep 1:

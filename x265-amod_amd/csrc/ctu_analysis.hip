@@ -40,7 +40,7 @@ using namespace xa_inter;
 /* X265AMD_TIMING=1: wall time per analysis stage, printed per frame by x265amd_analyse_frame */
 static double g_stageMs[8];
 static const char* const g_stageName[8] = { "merge", "search", "rdInter", "rdIntra", "bidir", "copies", "intraSlice", "other" };
-static bool g_timing = getenv("X265AMD_TIMING") != nullptr;
+static bool g_timing = xa_env_present("X265AMD_TIMING");
 static std::atomic<uint64_t> g_aheadStat[4];      /* X265AMD_TIMING: searches started ahead of a leaf's merge check, searches collected, started behind the merge check of a CU with sub-CUs, results the sub-CUs' restriction ruled out */
 static std::atomic<uint64_t> g_chainStat[4], g_chainTicks[8], g_cuStat[2][4][4];      /* [B / P][depth][skipped on the device, merge check on the host, search, intra try] */     /* X265AMD_TIMING: skip chains run, CUs they skipped, stops (not a skip / vector beyond what is published); the device's stage clock */
 struct StageTimer
@@ -459,11 +459,11 @@ struct Analyzer
         }
         J.tu_log2_max = si->tu_log2_max;
         J.ctu_x = ctuX; J.ctu_y = ctuY; J.lambda = lambda; J.lambda2 = lambda2; J.psy_rd = psyRd;
-        { static const int dbg = getenv("X265AMD_CHAIN_DBG") ? atoi(getenv("X265AMD_CHAIN_DBG")) : 0; J.dbg = dbg; }
+        J.dbg = 0;          /* (bits that leave single stores of the chain out: for timing them, never for a stream) */
         /* the 64x64 CU with levels decided on the device (chain_merge_rd64): built, verified candidate by candidate (X265AMD_CHAIN_VERIFY=2) and measured as no gain -- the
          * twelve units' chains take on the device what the host's two round trips took, and the pictures' links are the last column's searched CTUs either way -- so it
          * stays off unless asked for (X265AMD_CHAIN_64=1); the host's merge check goes on from the device's candidate instead (chainMergeFrom) */
-        { static const bool on64 = getenv("X265AMD_CHAIN_64") && atoi(getenv("X265AMD_CHAIN_64")) != 0; J.chain64_off = !on64; }
+        { static const bool on64 = xa_env_nonzero("X265AMD_CHAIN_64"); J.chain64_off = !on64; }
         J.rd_level = A->rd_level; J.sign_hide = si->sign_hide != 0; J.max_cu_depth = si->max_cu_depth;
         if (!chain.dScratch.p && chain.dScratch.alloc(x265amd_inter_rd_scratch_bytes()) != hipSuccess) return fail("chain scratch");
         J.scratch = (uint64_t)(uintptr_t)chain.dScratch.p;
@@ -558,9 +558,8 @@ struct Analyzer
     int chainMerge(int node, int x, int y, int depth, bool& taken)
     {
         taken = false;
-        static const bool on = !(getenv("X265AMD_CHAIN_MERGE") && atoi(getenv("X265AMD_CHAIN_MERGE")) == 0);
         /* (rd 2 reads the source block's mean and deviation from the merge check's measurement -- complexityCheckCU -- which the device's record does not carry) */
-        if (!on || A->rd_level < 3 || chain.status[node] != 2 || chain.stopNode != node || chain.stop.valid != 1 || chain.stop.node != (uint32_t)node) return 0;
+        if (A->rd_level < 3 || chain.status[node] != 2 || chain.stopNode != node || chain.stop.valid != 1 || chain.stop.node != (uint32_t)node) return 0;
         XA_HOSTPROF("an.chainMerge");
         const XaChainStop& c = chain.stop;
         ModeDepth& d = md[depth];
@@ -625,8 +624,7 @@ struct Analyzer
     int chainMergeFrom(int node, int x, int y, int depth, bool& taken)
     {
         taken = false;
-        static const bool on = !(getenv("X265AMD_CHAIN_MERGE_FROM") && atoi(getenv("X265AMD_CHAIN_MERGE_FROM")) == 0);
-        if (!on || A->rd_level < 3 || rp.rdoq_level || chain.status[node] != 2 || chain.stopNode != node || chain.stop.valid != 2 || chain.stop.node != (uint32_t)node) return 0;
+        if (A->rd_level < 3 || rp.rdoq_level || chain.status[node] != 2 || chain.stopNode != node || chain.stop.valid != 2 || chain.stop.node != (uint32_t)node) return 0;
         XA_HOSTPROF("an.chainMergeFrom");
         const XaChainStop& c = chain.stop;
         ModeDepth& d = md[depth];
@@ -662,7 +660,7 @@ struct Analyzer
     {
         skipped = false;
         if (chain.status[node] == 0) { if (runChain(node, depth)) return err; }
-        static const bool verify = getenv("X265AMD_CHAIN_VERIFY") != nullptr;
+        static const bool verify = xa_env_present("X265AMD_CHAIN_VERIFY");
         if (verify && chain.status[node] == 2 && chain.stopNode == node)
         {
             /* the device carried the entropy coder's state from CU to CU on its own: where it stopped it must be what the host arrives with */
@@ -1120,7 +1118,7 @@ struct Analyzer
     int fusedBuild(int x, int y, int depth, uint32_t refMask, XaSearchJob& J, bool& ok)
     {
         ok = false;
-        static const bool on = !(getenv("X265AMD_FUSED_SEARCH") && atoi(getenv("X265AMD_FUSED_SEARCH")) == 0);
+        static const bool on = xa_env_on("X265AMD_FUSED_SEARCH");
         const int log2 = 6 - depth, size = 1 << log2;
         const int method = S->search_method & 0x7f;
         if (!on || I->is_inter_b || S->weighted || !xa_is_queue(st) || S->subpel_refine > 2 || (method != X265AMD_ME_DIA && method != X265AMD_ME_HEX && method != X265AMD_ME_STAR) ||
@@ -1233,7 +1231,7 @@ struct Analyzer
      * queue), or behind the merge check of a CU whose sub-CUs come first (the third queue) */
     int searchAhead(int x, int y, int depth, bool leaf)
     {
-        static const int on = getenv("X265AMD_SEARCH_AHEAD") ? atoi(getenv("X265AMD_SEARCH_AHEAD")) : 3;      /* bit 0: leaves, bit 1: CUs with sub-CUs */
+        static const int on = xa_env_int("X265AMD_SEARCH_AHEAD", 3);      /* bit 0: leaves, bit 1: CUs with sub-CUs */
         if (!(on & (leaf ? 1 : 2))) return 0;
         void* aux = xa_queue_aux(st);
         void* q = leaf ? aux : (aux && xa_queue_aux(aux) ? xa_queue_aux(aux) : aux);
@@ -1360,8 +1358,7 @@ struct Analyzer
         x265amd_me_detail& det = d.det;
         x265amd_inter_search_params sp = *S;
         sp.qp = lambdaQp; sp.chroma_mc = A->rd_level >= 3;        /* bChromaMC = m_bChromaSa8d: below rd 3 the search is luma only (no chroma SATD either) */
-        static const bool lazyMc = !(getenv("X265AMD_LAZY_MC") && atoi(getenv("X265AMD_LAZY_MC")) == 0);
-        sp.lazy_sync = !searchOnly && lazyMc;       /* the measurement below waits for the final prediction */
+        sp.lazy_sync = !searchOnly;       /* the measurement below waits for the final prediction */
         const uint32_t masks[2] = { refMask, 0 };
         xa_phase(XA_PH_ANALYZER);
         struct PhEnd { ~PhEnd() { xa_phase(XA_PH_INTER_SEARCH); } } phEnd;
@@ -1471,8 +1468,7 @@ struct Analyzer
         int32_t bits = 0;
         x265amd_inter_search_params sp = *S;
         sp.qp = lambdaQp; sp.chroma_mc = A->rd_level >= 3;        /* bChromaMC = m_bChromaSa8d: below rd 3 the search is luma only (no chroma SATD either) */
-        static const bool lazyMc = !(getenv("X265AMD_LAZY_MC") && atoi(getenv("X265AMD_LAZY_MC")) == 0);
-        sp.lazy_sync = !searchOnly && lazyMc;
+        sp.lazy_sync = !searchOnly;
         int rc = x265amd_pred_inter_search_ex(me, st, I, &sp, cur, col, planes, numPics, stride, cstride, &c, 1, pu, &bits, tileAddr(m.predTile), tileBytes, nullptr, refMasks);
         if (rc != X265AMD_OK) return err = rc;
         for (int i = 0; i < n4 * n4; i++) { m.u[i].pred_mode = X265AMD_MODE_INTER; m.u[i].part_size = (uint8_t)part; }
@@ -1807,10 +1803,9 @@ struct Analyzer
                 const uint64_t tiles2[2] = { tileAddr(predTile(depth + 1, PRED_INTRA)), tileAddr(reconTile(depth + 1, PRED_INTRA)) };
                 /* while the chain runs the CU's own 2Nx2N evaluation (started on its queue above) is collected: its bits are counted on the host */
                 struct Between { Analyzer* a; int x, y, depth; bool done; int rc; } bt{ this, x, y, depth, false, 0 };
-                static const bool overlap = !(getenv("X265AMD_INTRA_COLLECT_EARLY") && atoi(getenv("X265AMD_INTRA_COLLECT_EARLY")) == 0);
                 const int qrc = xa_intra_quad8_ws(st, si, &rp, units, planes + 3 * (numPics - 1), planes + 3 * (numPics - 2), stride, cstride, x, y, qp, d.cur.ctx, d.cur.frac,
                                                   tileAddr(split.reconTile), tilesN, tiles2, r4, &intraWs,
-                                                  deferred && overlap ? [](void* c) { Between* b = (Between*)c; b->rc = b->a->rdIntra(b->a->md[b->depth].pred[PRED_INTRA], b->x, b->y, b->depth, PRED_INTRA, true, 0); b->done = true; } : (void (*)(void*))nullptr,
+                                                  deferred ? [](void* c) { Between* b = (Between*)c; b->rc = b->a->rdIntra(b->a->md[b->depth].pred[PRED_INTRA], b->x, b->y, b->depth, PRED_INTRA, true, 0); b->done = true; } : (void (*)(void*))nullptr,
                                                   &bt, lambdaQp != qp ? lambdaQp : 0);
                 if (bt.done) { if (bt.rc) return err; deferredDone = true; }
                 if (qrc < 0) return err = qrc;
@@ -1818,7 +1813,7 @@ struct Analyzer
                 {
                     XA_HOSTPROF("an.compressIntra chain results");
                     chained = true;
-                    if (const char* lg = getenv("X265AMD_CHAIN_LOG"))
+                    if (const char* lg = xa_env_str("X265AMD_CHAIN_LOG"))
                     {
                         int lx = -1, ly = -1;
                         if (sscanf(lg, "%d,%d", &lx, &ly) == 2 && (lx & ~15) == x && (ly & ~15) == y)
@@ -1878,7 +1873,7 @@ struct Analyzer
                     if (childQp(depth, q)) return err;
                     if (compressIntra(cx, cy, depth + 1)) return err;
                     const Mode& nb = *md[depth + 1].best;
-                    if (const char* lg = depth == 2 ? getenv("X265AMD_CHAIN_LOG") : nullptr)
+                    if (const char* lg = depth == 2 ? xa_env_str("X265AMD_CHAIN_LOG") : nullptr)
                     {
                         int lx = -1, ly = -1;
                         if (sscanf(lg, "%d,%d", &lx, &ly) == 2 && (lx & ~15) == x && (ly & ~15) == y)
@@ -1975,8 +1970,7 @@ struct Analyzer
             {
                 /* a CU that cannot split at the head of a chain: its search and its intra try start beside the merge check (the conditions of step 3's checkInterFused) */
                 if (searchAhead(x, y, depth, true)) return err;
-                static const bool specIntraOn = !(getenv("X265AMD_INTRA_AHEAD_LEAF") && atoi(getenv("X265AMD_INTRA_AHEAD_LEAF")) == 0);
-                if (specIntraOn && log2 != 6 && xa_is_queue(st))
+                if (log2 != 6 && xa_is_queue(st))
                 {
                     const int b = intraBegin(x, y, depth);
                     if (b < 0) return err = b;
@@ -1985,7 +1979,7 @@ struct Analyzer
             }
             if (chain.on && chainSkip(node, x, y, depth, devSkip)) return err;
             if (g_timing) g_cuStat[si->slice_type == 1][depth][devSkip ? 0 : 1]++;
-            static const bool verify2 = getenv("X265AMD_CHAIN_VERIFY") && atoi(getenv("X265AMD_CHAIN_VERIFY")) >= 2;
+            static const bool verify2 = xa_env_int("X265AMD_CHAIN_VERIFY", 0) >= 2;
             if (devSkip && verify2)
             {
                 /* debugging: the host's own merge check of the CU the device skipped must arrive at the same mode, cost and coder state */
@@ -2006,7 +2000,7 @@ struct Analyzer
                 chain.frDirty[depth] = true;            /* this CU is the host's: what the chain decides below it stays inside it */
                 bool devMerge = false;
                 if (chain.on && chainMerge(node, x, y, depth, devMerge)) return err;
-                static const bool verify3 = getenv("X265AMD_CHAIN_VERIFY") && atoi(getenv("X265AMD_CHAIN_VERIFY")) >= 2;
+                static const bool verify3 = xa_env_int("X265AMD_CHAIN_VERIFY", 0) >= 2;
                 if (devMerge && verify3)
                 {
                     /* debugging: the host's own merge check must leave the same two modes */
@@ -2134,7 +2128,7 @@ struct Analyzer
                 if (!(A->rect || A->amp) && checkInterFused(x, y, depth, allSplitRefs, fused)) return err;
                 if (fused)
                 {
-                    static const bool verifyS = getenv("X265AMD_CHAIN_VERIFY") && atoi(getenv("X265AMD_CHAIN_VERIFY")) >= 2;
+                    static const bool verifyS = xa_env_int("X265AMD_CHAIN_VERIFY", 0) >= 2;
                     if (verifyS)
                     {
                         /* debugging: the ordinary search and rate-distortion of the same CU must give the same mode */
@@ -2339,9 +2333,9 @@ static int compress_ctu_impl(x265amd_me_ctx* me, void* stream, const x265amd_mvp
      * (after) to <dir>/ctu_<addr>.bin so that the reference's compressCTU can be run on exactly the same state (dbg/ctu_replay.py) */
     FILE* dump = nullptr;
     int dumpMx = 0, dumpMy = 0;
-    if (const char* dir = getenv("X265AMD_DUMP_CTU"))
+    if (const char* dir = xa_env_str("X265AMD_DUMP_CTU"))
     {
-        const char* poc = getenv("X265AMD_DUMP_POC"); const char* mg = getenv("X265AMD_DUMP_MARGIN");
+        const char* poc = xa_env_str("X265AMD_DUMP_POC"); const char* mg = xa_env_str("X265AMD_DUMP_MARGIN");
         if (poc && mg && atoi(poc) == I->poc && sscanf(mg, "%d,%d", &dumpMx, &dumpMy) == 2)
         {
             char path[512];
@@ -2416,14 +2410,13 @@ static int compress_ctu_impl(x265amd_me_ctx* me, void* stream, const x265amd_mvp
         {
             /* the skip chain (inter_chain_dev.h): what it assumes of the configuration -- a skipped CU ends there (early skip + recursion skip), one transform size per
              * plane, plain quantisation -- and a device job queue to run on */
-            static const bool chainEnv = !(getenv("X265AMD_INTER_CHAIN") && atoi(getenv("X265AMD_INTER_CHAIN")) == 0);
+            static const bool chainEnv = xa_env_on("X265AMD_INTER_CHAIN");
             /* (a slice with weights: its predictions are weighted and its searches read weighted copies -- the host path does both; the chain does not) */
             /* under delta QP: cu_qp_delta is priced as rd 3-4 price it, and the device carries one QP for the quantiser and the lambdas (none of the CTU's above 51) */
             bool dqpOk = true;
             if (si->use_dqp)
             {
-                static const bool chainDqp = !(getenv("X265AMD_CHAIN_DQP") && atoi(getenv("X265AMD_CHAIN_DQP")) == 0);
-                dqpOk = chainDqp && A->rd_level >= 3;
+                dqpOk = A->rd_level >= 3;
                 for (int k = 0; k < (si->max_cu_dqp_depth ? 5 : 1); k++) dqpOk = dqpOk && a.cuQp[k] <= 51;
             }
             a.chain.on = chainEnv && !S->weighted && si->slice_type != 2 && A->rd_level <= 4 && A->early_skip && A->rskip == 1 && !A->rdoq_level && si->tu_max_depth_inter == 1 && dqpOk &&
@@ -2504,7 +2497,7 @@ int xa_analyse_frame(x265amd_me_ctx* me, void* stream, const x265amd_mvpred_info
     struct TmpMap { const x265amd_mv_unit* h = nullptr; ~TmpMap() { if (h) xa_devmap_unregister(h); } } tmpCur, tmpCol;
     XaMapUnit* frameDCur = (XaMapUnit*)xa_devmap_find(cur);
     const XaMapUnit* frameDCol = (const XaMapUnit*)xa_devmap_find(col);
-    if (xa_queues_enabled() && !getenv("X265AMD_DUMP_CTU"))
+    if (xa_queues_enabled() && !xa_env_present("X265AMD_DUMP_CTU"))
     {
         if (!frameDCur && (frameDCur = (XaMapUnit*)xa_devmap_register(cur, (size_t)w4 * h4)) != nullptr) tmpCur.h = cur;
         if (col && !frameDCol && si->slice_type != 2 && (frameDCol = (const XaMapUnit*)xa_devmap_register(col, (size_t)w4 * h4)) != nullptr)
@@ -2546,12 +2539,12 @@ int xa_analyse_frame(x265amd_me_ctx* me, void* stream, const x265amd_mvpred_info
     int rowThreads = 1;
     if (wpp && ctuH > 1 && ctuW > 1)
     {
-        const char* e = getenv("X265AMD_ROW_THREADS");
+        const char* e = xa_env_str("X265AMD_ROW_THREADS");
         rowThreads = e ? atoi(e) : 64;        /* the wavefront never holds more than min(rows, columns / 2) CTUs at once */
         if (rowThreads > ctuH) rowThreads = ctuH;
         if (rowThreads > (ctuW + 1) / 2) rowThreads = (ctuW + 1) / 2;
     }
-    const bool dumping = getenv("X265AMD_DUMP_CTU") != nullptr;        /* the dump synchronises the device: not behind a resident kernel */
+    const bool dumping = xa_env_present("X265AMD_DUMP_CTU");        /* the dump synchronises the device: not behind a resident kernel */
     if (rowThreads <= 1)
     {
         if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) rc = xa_fail(X265AMD_EHIP, "analyse_frame: synchronize");
@@ -2625,14 +2618,7 @@ int xa_analyse_frame(x265amd_me_ctx* me, void* stream, const x265amd_mvpred_info
                 st = own;
             }
             {
-                /* the last rows of a picture are what the pictures behind it wait for (and a cut last row is a picture's slowest): their waits for the device poll a
-                 * while before the task parks (X265AMD_SPIN_US: microseconds, X265AMD_SPIN_ROWS: how many rows from the bottom; 0 = park at once) */
-                static const int spinUs = getenv("X265AMD_SPIN_US") ? atoi(getenv("X265AMD_SPIN_US")) : 0;
-                static const int spinRows = getenv("X265AMD_SPIN_ROWS") ? atoi(getenv("X265AMD_SPIN_ROWS")) : 1;
-                if (spinUs > 0 && row >= f.ctuH - spinRows) xa_task_spin_ns((uint64_t)spinUs * 1000);
-            }
-            {
-                static const char* const lg = getenv("X265AMD_QUEUE_LOG");
+                static const char* const lg = xa_env_str("X265AMD_QUEUE_LOG");
                 int lp = -1, lr = -1;
                 if (lg && sscanf(lg, "%d,%d", &lp, &lr) == 2 && lp == f.poc && lr == row && st && !own) xa_queue_log(st, lp, lr);
             }
@@ -2641,7 +2627,7 @@ int xa_analyse_frame(x265amd_me_ctx* me, void* stream, const x265amd_mvpred_info
             void* helper2 = helper ? xa_queue_try_acquire() : nullptr;         /* and a third and a fourth: the 16x16 / 32x32 CUs' 2Nx2N evaluations beside their sub-CUs */
             void* helper3 = helper2 ? xa_queue_try_acquire() : nullptr;
             /* P pictures: a second queue for the searches that start ahead of their CU's merge check (Analyzer::searchAhead) */
-            static const int auxSpare = getenv("X265AMD_AUX_SPARE") ? atoi(getenv("X265AMD_AUX_SPARE")) : 112;       /* (an I picture started meanwhile needs four queues per row) */
+            const int auxSpare = 112;       /* (an I picture started meanwhile needs four queues per row) */
             void* aux = (f.pSlice && st && !own) ? xa_queue_try_acquire_spare(auxSpare) : nullptr;
             void* aux2 = aux ? xa_queue_try_acquire_spare(auxSpare) : nullptr;                /* and a third for the searches of CUs whose sub-CUs come first */
             if (aux) xa_queue_set_aux(st, aux);
@@ -2658,8 +2644,7 @@ int xa_analyse_frame(x265amd_me_ctx* me, void* stream, const x265amd_mvpred_info
                  * without its second to fourth queue its CTUs take twice as long */
                 /* a row of a P picture likewise: the rows that started while an I picture held the queues (in lockstep behind it) are the ones still running when it has
                  * ended -- the tail of the clip, where every link is a last-column CTU searched CU by CU -- and the searches ahead of the merge checks need the second and third queue */
-                static const bool auxRetry = !(getenv("X265AMD_AUX_RETRY") && atoi(getenv("X265AMD_AUX_RETRY")) == 0);
-                if (auxRetry && f.pSlice && st && !own && !aux2)
+                if (f.pSlice && st && !own && !aux2)
                 {
                     if (!aux) { aux = xa_queue_try_acquire_spare(auxSpare); if (aux) xa_queue_set_aux(st, aux); }
                     if (aux && !aux2) { aux2 = xa_queue_try_acquire_spare(auxSpare); if (aux2) xa_queue_set_aux(aux, aux2); }
@@ -2683,8 +2668,8 @@ int xa_analyse_frame(x265amd_me_ctx* me, void* stream, const x265amd_mvpred_info
                 int r2 = f.firstErr.load();
                 if (r2 == X265AMD_OK && !st) r2 = X265AMD_EHIP;
                 /* the reference pictures are published column by column: this CTU follows them (parked on their counters meanwhile) */
-                static const bool ctuLog = getenv("X265AMD_CTU_LOG") != nullptr;
-                static const int ctuLogPoc = ctuLog && getenv("X265AMD_CTU_LOG")[0] == 'p' ? atoi(getenv("X265AMD_CTU_LOG") + 1) : -1;       /* "p9": every row of picture 9; anything else: the last three rows of every picture */
+                static const bool ctuLog = xa_env_present("X265AMD_CTU_LOG");
+                static const int ctuLogPoc = ctuLog && xa_env_str("X265AMD_CTU_LOG")[0] == 'p' ? atoi(xa_env_str("X265AMD_CTU_LOG") + 1) : -1;       /* "p9": every row of picture 9; anything else: the last three rows of every picture */
                 static const auto tLog0 = std::chrono::steady_clock::time_point() + std::chrono::duration_cast<std::chrono::steady_clock::duration>(std::chrono::duration<double, std::milli>(
                     floor(std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count() / 1e6) * 1e6));       /* milliseconds modulo 10^6 of the steady clock: X265AMD_PUB_LOG's clock */
                 const double tA = ctuLog ? std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tLog0).count() : 0;

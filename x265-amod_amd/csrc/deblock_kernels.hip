@@ -226,8 +226,7 @@ extern "C" int x265amd_deblock_rows_cols(void* stream, x265amd_pixel* d_y, x265a
     P.bypassEnabled = bypassEnabled; P.y4Begin = y4_begin; P.y4End = y4_end;
     P.xvBegin = 16 * ctu_col_begin + 1; P.xvEnd = 16 * ctu_col_end + 1; P.xhBegin = 16 * ctu_col_begin; P.xhEnd = 16 * ctu_col_end;
     const int w4 = width >> 2, h4 = y4_end - y4_begin;
-    static const bool fuse = !(getenv("X265AMD_DEBLOCK_FUSED") && atoi(getenv("X265AMD_DEBLOCK_FUSED")) == 0);
-    if (fuse && passes == 3 && ctu_col_end - ctu_col_begin <= 8)
+    if (passes == 3 && ctu_col_end - ctu_col_begin <= 8)
     {
         hipLaunchKernelGGL(k_deblock_unit, dim3(1), dim3(256), 0, (hipStream_t)stream, P);
         hipError_t e = hipGetLastError();

@@ -507,7 +507,7 @@ __global__ __launch_bounds__(64 * XA_SERVER_WAVES) void k_job_server(XaRingDev* 
     __shared__ int s_go;
     __shared__ unsigned long long s_prof[64];
     __shared__ unsigned long long s_sized[24];
-    /* base: the first queue of this launch (the server's queues are served by two launches: the second starts when the first's queues are all taken -- Server::startSecond) */
+    /* base: the first queue of this launch (0: one launch serves every queue -- Server::start) */
     const int qIdx = base + (int)blockIdx.x;
     XaRingDev* rd = rings + qIdx;
     XaRingHost* rh = hosts + qIdx;
@@ -737,7 +737,7 @@ namespace {
 
 void dump_debug_areas(int);
 std::atomic<uint64_t> g_waitNs(0), g_heldNs(0), g_waits(0), g_depNs(0);
-const bool g_prof = getenv("X265AMD_QUEUE_PROF") != nullptr;
+const bool g_prof = xa_env_present("X265AMD_QUEUE_PROF");
 
 /* the number of queues when X265AMD_QUEUES does not say: a resident workgroup on 224 of the 256 CUs.  Measured: 1080p encodes the same with 128 and with 224
  * (26.1 / 26.2 frames/s over three alternating runs each); 2160p, whose I pictures want up to four queues for each of 34 CTU rows, 9.9 against 12.8 */
@@ -753,20 +753,12 @@ struct Server
     char* staging = nullptr;
     std::vector<XaQueue> q;
     hipStream_t stream = nullptr;
-    /* The queues are served by TWO launches of the resident kernel (round 5): the first `firstCount` queues from the start, the rest from the moment a queue beyond them is
-     * handed out (queues are taken lowest index first).  A resident workgroup holds a whole compute unit (144 KB of LDS, 256 vector registers per lane): with all 224 resident
-     * from the first picture on, everything else -- the lookahead's cost estimates above all, whose first decision is 384 estimates -- ran on the 32 units left (527 ms at
-     * 2160p against 298 on an idle device, longer than the I picture beside it).  While only the I picture runs, its rows need a fraction of the queues.  The second launch
-     * has a stream of the OTHER extreme priority: like the first it must not share a hardware queue with anything (see init). */
-    hipStream_t stream2 = nullptr;
-    int firstCount = 0;
-    bool running2 = false;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;        /* around every launch of the resident kernel, on its stream: its duration by HIP events (bench.py's roofline) */
     double kernelMs = 0.0; uint64_t launches = 0;
     bool running = false;
     int refs = 0;
     uint64_t generation = 0;
-    bool disabled = false, ringsInHost = false;
+    bool disabled = false;
     volatile uint64_t freeCount = 0;            /* queues not taken (what parked row tasks watch; changed under the lock) */
 
     int init()
@@ -774,16 +766,12 @@ struct Server
         if (numQueues) return 0;
         xa_bind_device();
         xa_thread_device();
-        const char* e = getenv("X265AMD_QUEUES");
+        const char* e = xa_env_str("X265AMD_QUEUES");
         int n = e ? atoi(e) : g_queuesHint.load();
         if (n <= 0) { disabled = true; return -1; }
         if (n > 224) n = 224;
-        ringsInHost = getenv("X265AMD_RING_HOST") != nullptr;
-        if (ringsInHost ? hipHostMalloc((void**)&rings, sizeof(XaRingDev) * n, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess
-                        : hipExtMallocWithFlags((void**)&rings, sizeof(XaRingDev) * n, hipDeviceMallocUncached) != hipSuccess)
-            return -1;
-        if (!ringsInHost && (hipMemset(rings, 0, sizeof(XaRingDev) * n) != hipSuccess || hipDeviceSynchronize() != hipSuccess)) return -1;
-        if (ringsInHost) memset((void*)rings, 0, sizeof(XaRingDev) * n);
+        if (hipExtMallocWithFlags((void**)&rings, sizeof(XaRingDev) * n, hipDeviceMallocUncached) != hipSuccess) return -1;
+        if (hipMemset(rings, 0, sizeof(XaRingDev) * n) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return -1;
         if (hipHostMalloc((void**)&hosts, sizeof(XaRingHost) * n, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) return -1;
         if (hipHostMalloc((void**)&staging, kStagingBytes * n, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) return -1;
         /* The resident kernel must not share a hardware queue with anything: a kernel launched behind it on the same hardware queue waits until it
@@ -794,18 +782,6 @@ struct Server
             if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess || hipStreamCreateWithPriority(&stream, hipStreamNonBlocking, greatest) != hipSuccess)
                 if (hipStreamCreateWithFlags(&stream, hipStreamNonBlocking) != hipSuccess) return -1;
         }
-        {
-            const char* f = getenv("X265AMD_QUEUES_FIRST");
-            /* Measured (profiles/r05_queues_first_sweep.txt): with 96 or 128 first the lookahead's first decision falls from 135 to 89 ms at 1080p (518 -> 499 at 2160p, whose
-             * I picture wants more than that many queues within 170 ms), but the 20-frame encodes are not faster (0.38 -> 0.39 s at 1080p: a queue handed out whose workgroup has
-             * still to find a free compute unit among the lookahead's long-running rows stalls its row) -- so the default stays ONE launch of everything; X265AMD_QUEUES_FIRST=n
-             * is the experiment */
-            firstCount = f ? atoi(f) : n;
-            if (firstCount <= 0 || firstCount > n) firstCount = n;
-            int least = 0, greatest = 0;
-            if (firstCount < n && (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess || least == greatest || hipStreamCreateWithPriority(&stream2, hipStreamNonBlocking, least) != hipSuccess))
-            { stream2 = nullptr; firstCount = n; }         /* no second priority to be had: one launch, as before */
-        }
         if (hipFuncSetAttribute((const void*)k_job_server, hipFuncAttributeMaxDynamicSharedMemorySize, XA_SERVER_LDS) != hipSuccess) return -1;
         if (hipEventCreate(&ev0) != hipSuccess || hipEventCreate(&ev1) != hipSuccess) return -1;
         memset((void*)hosts, 0, sizeof(XaRingHost) * n);
@@ -813,7 +789,7 @@ struct Server
         for (int i = 0; i < n; i++) { q[i].idx = i; q[i].rd = rings + i; q[i].rh = hosts + i; q[i].staging = staging + kStagingBytes * i; }
         numQueues = n;
         freeCount = n;
-        if (getenv("X265AMD_QUEUE_DEBUG") && (atoi(getenv("X265AMD_QUEUE_DEBUG")) & 2)) signal(SIGABRT, dump_debug_areas);
+        if (xa_env_int("X265AMD_QUEUE_DEBUG", 0) & 2) signal(SIGABRT, dump_debug_areas);
         return 0;
     }
     /* called with the lock held */
@@ -834,20 +810,12 @@ struct Server
         }
         _mm_sfence();
         (void)hipEventRecord(ev0, stream);
-        hipLaunchKernelGGL(k_job_server, dim3(firstCount), dim3(64 * XA_SERVER_WAVES), XA_SERVER_LDS, stream, rings, hosts, 100000000LL * 60, generation, 0);
+        /* ONE launch of every queue's workgroup.  (A first launch of 96 or 128 queues with the rest behind it when wanted gave the lookahead's first decision more of the
+         * device -- 135 -> 89 ms at 1080p -- but no faster encode: profiles/r05_queues_first_sweep.txt) */
+        hipLaunchKernelGGL(k_job_server, dim3(numQueues), dim3(64 * XA_SERVER_WAVES), XA_SERVER_LDS, stream, rings, hosts, 100000000LL * 60, generation, 0);
         if (hipGetLastError() != hipSuccess) return -1;
         (void)hipEventRecord(ev1, stream);
-        running = true; running2 = false;
-        return 0;
-    }
-    /* called with the lock held, the first launch running: the queues from firstCount on get their workgroups */
-    int startSecond()
-    {
-        if (running2 || firstCount >= numQueues) return 0;
-        xa_thread_device();
-        hipLaunchKernelGGL(k_job_server, dim3(numQueues - firstCount), dim3(64 * XA_SERVER_WAVES), XA_SERVER_LDS, stream2, rings, hosts, 100000000LL * 60, generation, firstCount);
-        if (hipGetLastError() != hipSuccess) return -1;
-        running2 = true;
+        running = true;
         return 0;
     }
     void stop()
@@ -856,10 +824,9 @@ struct Server
         for (int i = 0; i < numQueues; i++) rings[i].quit = 1;
         _mm_sfence();
         (void)hipStreamSynchronize(stream);
-        if (running2) (void)hipStreamSynchronize(stream2);
-        running = false; running2 = false;
+        running = false;
         { float ms = 0.f; if (hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) { kernelMs += ms; launches++; } }
-        static const bool prof = getenv("X265AMD_QUEUE_PROF") != nullptr;
+        static const bool prof = xa_env_present("X265AMD_QUEUE_PROF");
         if (prof) profile_report(false);
     }
     void profile_report(bool final)
@@ -997,7 +964,7 @@ void xa_server_alive();
 std::atomic<uint64_t> g_pushNs{ 0 }, g_pushN{ 0 };
 int q_push(XaQueue* q, uint32_t op, uint32_t flags, uint32_t count, const void* args, size_t argBytes)
 {
-    static const bool timing = getenv("X265AMD_TIMING") != nullptr;
+    static const bool timing = xa_env_present("X265AMD_TIMING");
     struct PushTimer { bool on; std::chrono::steady_clock::time_point t0; ~PushTimer() { if (on) { g_pushNs += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count(); g_pushN++; } } }
         pt{ timing, timing ? std::chrono::steady_clock::now() : std::chrono::steady_clock::time_point() };
     if (argBytes > sizeof(uint64_t) * XA_CMD_ARG_WORDS) return -1;
@@ -1005,7 +972,7 @@ int q_push(XaQueue* q, uint32_t op, uint32_t flags, uint32_t count, const void* 
     if (q->submitted >= XA_RING && q_wait(q, q->submitted - XA_RING + 1)) return -1;        /* the slot must have been consumed */
     XaCmd c;
     memset(&c, 0, sizeof(c));
-    static const uint32_t debugBits = getenv("X265AMD_QUEUE_DEBUG") ? (uint32_t)atoi(getenv("X265AMD_QUEUE_DEBUG")) : 0;
+    static const uint32_t debugBits = (uint32_t)xa_env_int("X265AMD_QUEUE_DEBUG", 0);
     c.op = op; c.flags = flags; c.count = count; c.reserved = debugBits;
     if (argBytes) memcpy(c.args, args, argBytes);
     {
@@ -1051,7 +1018,7 @@ void xa_thread_device() { const int d = g_device.load(); if (d >= 0) (void)hipSe
 /* ---- X265AMD_TIMING: host phases of the row tasks ---- */
 namespace {
 std::atomic<uint64_t> g_phaseNs[XA_PH_COUNT], g_phaseN[XA_PH_COUNT];
-const bool g_phases = getenv("X265AMD_TIMING") != nullptr;
+const bool g_phases = xa_env_present("X265AMD_TIMING");
 }
 void xa_phase(int k)
 {
@@ -1080,7 +1047,7 @@ int xa_queues_hint(int n)
     if (n > 224) n = 224;
     int cur = g_queuesHint.load();
     while (n > cur && !g_queuesHint.compare_exchange_weak(cur, n)) {}
-    const char* e = getenv("X265AMD_QUEUES");
+    const char* e = xa_env_str("X265AMD_QUEUES");
     return e ? atoi(e) : g_queuesHint.load();
 }
 
@@ -1126,7 +1093,7 @@ void* xa_queue_acquire()
         }
         if (S.freed.wait_for(g, std::chrono::seconds(120)) == std::cv_status::timeout) return nullptr;
     }
-    if (S.start() != 0 || (f->idx >= S.firstCount && S.startSecond() != 0)) return nullptr;
+    if (S.start() != 0) return nullptr;
     __atomic_fetch_add(&S.hosts[0].alive, 1, __ATOMIC_RELAXED);
     f->busy = true; f->stagingUsed = 0; f->stagingUsedOut = 0; f->deferred.clear(); f->helper = nullptr; f->aux = nullptr;
     S.freeCount = S.freeCount - 1;
@@ -1142,20 +1109,19 @@ void* xa_queue_acquire()
 /* a second queue for the holder of a first one, if one is free right now: never waits (the rows of a picture take their FIRST queues in row order so that
  * waiting for one always ends; a second queue is a bonus) */
 void* xa_queue_try_acquire() { return xa_queue_try_acquire_spare(-1); }
-/* ... with the number of queues that must stay free given by the caller (-1: X265AMD_HELPER_SPARE, default 24): the extra queues of a P picture's rows are a
+/* ... with the number of queues that must stay free given by the caller (-1: 24): the extra queues of a P picture's rows are a
  * convenience and leave half of the queues alone, the extra queues of an I picture's rows halve its time and take what there is */
 void* xa_queue_try_acquire_spare(int spareWanted)
 {
     Server& S = server();
     std::unique_lock<std::mutex> g(S.m);
     if (S.disabled || S.init() != 0) return nullptr;
-    static const int spareDefault = getenv("X265AMD_HELPER_SPARE") ? atoi(getenv("X265AMD_HELPER_SPARE")) : 24;       /* queues left to the rows that need a first one */
-    const int spare = spareWanted >= 0 ? spareWanted : spareDefault;
+    const int spare = spareWanted >= 0 ? spareWanted : 24;       /* queues left to the rows that need a first one */
     int freeN = 0;
     XaQueue* f = nullptr;
     for (XaQueue& x : S.q) if (!x.busy) { freeN++; if (!f) f = &x; }
     if (!f || freeN <= spare) return nullptr;
-    if (S.start() != 0 || (f->idx >= S.firstCount && S.startSecond() != 0)) return nullptr;
+    if (S.start() != 0) return nullptr;
     f->busy = true; f->stagingUsed = 0; f->stagingUsedOut = 0; f->deferred.clear(); f->helper = nullptr; f->aux = nullptr;
     S.freeCount = S.freeCount - 1;
     S.refs++;
@@ -1209,7 +1175,7 @@ void xa_queue_release(void* st)
     S.freeCount = S.freeCount + 1;
     S.freed.notify_one();
     if (g_prof) g_heldNs += (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - q->acquired).count();
-    if (getenv("X265AMD_QUEUE_DEBUG") && q->rh->dbg[63]) fprintf(stderr, "x265amd queue %d: %llu command slot re-reads so far\n", q->idx, (unsigned long long)q->rh->dbg[63]);
+    if (xa_env_present("X265AMD_QUEUE_DEBUG") && q->rh->dbg[63]) fprintf(stderr, "x265amd queue %d: %llu command slot re-reads so far\n", q->idx, (unsigned long long)q->rh->dbg[63]);
     if (--S.refs == 0) S.stop();
 }
 
@@ -1227,7 +1193,7 @@ void xa_q_next_flags(void* st, int flags) { if (xa_is_queue(st)) as_queue(st)->n
 
 hipError_t xa_q_enqueue(void* st, int op, const void* args, size_t argBytes, int count, int flags)
 {
-    static const bool trace = getenv("X265AMD_QUEUE_TRACE") != nullptr;     /* debugging: name every command and wait for it */
+    static const bool trace = xa_env_present("X265AMD_QUEUE_TRACE");     /* debugging: name every command and wait for it */
     XaQueue* q = as_queue(st);
     flags |= (int)q->nextFlags; q->nextFlags = 0;
     if (trace)
@@ -1240,7 +1206,7 @@ hipError_t xa_q_enqueue(void* st, int op, const void* args, size_t argBytes, int
         fflush(stderr);
         if (q_push(q, (uint32_t)op, (uint32_t)flags | XA_CMD_SIGNAL, (uint32_t)count, args, argBytes) || q_wait(q, q->submitted)) return hipErrorUnknown;
         fprintf(stderr, "  took %.1f us\n", std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t00).count() - tEnq);
-        static const bool verbose = getenv("X265AMD_QUEUE_TRACE")[0] == '2';
+        static const bool verbose = xa_env_str("X265AMD_QUEUE_TRACE")[0] == '2';
         if (!verbose) return hipSuccess;
         if (op == XA_OP_CU_MEASURE || op == XA_OP_MC)
             for (int w = 0; w < 8; w++)

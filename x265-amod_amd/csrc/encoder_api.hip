@@ -216,17 +216,16 @@ extern "C" x265amd_encoder* x265amd_encoder_open(const x265amd_param* p)
             /* The lookahead's kernels run for tens of milliseconds (a batch of cost estimates: hundreds of rows chained through progress words), and streams of one priority
              * share hardware queues: a picture's in-loop filter launch -- one workgroup, microseconds -- queued behind such a batch on the same hardware queue waited for it to END
              * (k_deblock_unit: 47 ms at worst in round 4's trace), and every picture that references that row waited with it.  Streams of another priority get hardware queues
-             * of their own (device_queue.hip: the resident kernel's is the highest): the lookahead takes the lowest.  X265AMD_LA_PRIORITY=0: the ordinary one, as before. */
-            static const bool laLow = !(getenv("X265AMD_LA_PRIORITY") && atoi(getenv("X265AMD_LA_PRIORITY")) == 0);
+             * of their own (device_queue.hip: the resident kernel's is the highest): the lookahead takes the lowest. */
             int least = 0, greatest = 0;
-            if (!laLow || hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess || least == greatest || hipStreamCreateWithPriority(&e->laStream, hipStreamNonBlocking, least) != hipSuccess)
+            if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess || least == greatest || hipStreamCreateWithPriority(&e->laStream, hipStreamNonBlocking, least) != hipSuccess)
                 if (hipStreamCreateWithFlags(&e->laStream, hipStreamNonBlocking) != hipSuccess) { xa_fail(X265AMD_EHIP, "encoder_open: stream"); return nullptr; }
         }
     }
     {
         /* pictures whose references are complete are analysed concurrently (B frames of a mini-GOP, the next P): the reference's frame threads, but
          * a picture only starts when its references are final, so the output does not depend on the thread count */
-        const char* ft = getenv("X265AMD_FRAME_THREADS");
+        const char* ft = xa_env_str("X265AMD_FRAME_THREADS");
         e->frameThreads = ft ? atoi(ft) : 3;
         if (e->frameThreads < 1) e->frameThreads = 1;
     }
@@ -242,7 +241,7 @@ extern "C" x265amd_encoder* x265amd_encoder_open(const x265amd_param* p)
         range += 8 / 2;
         range += 2 + (hpelIters[p->subpelRefine] + 1) / 2;
         e->refLagRows = 1 + ((range + 63) / 64);
-        if (!getenv("X265AMD_FRAME_THREADS"))
+        if (!xa_env_present("X265AMD_FRAME_THREADS"))
         {
             /* every CTU row in flight holds a device job queue; pictures in flight never wait for one */
             const int rowsInFlight = p->bEnableWavefront ? std::max(1, std::min(e->ctuH, (e->ctuW + 1) / 2)) : 1;
@@ -565,7 +564,6 @@ static int encoder_encode_impl(x265amd_encoder* e, x265amd_nal** ppNal, uint32_t
     {
         PicP pic(new Pic);
         pic->pool = e->laPool;
-        if (e->firstInMs < 0) e->firstInMs = Pic::pubClockMs();
         pic->poc = e->frameCount++;
         const auto tu0 = std::chrono::steady_clock::now();
         int rc = e->uploadPicture(picIn, *pic, inputOnDevice);
@@ -579,17 +577,16 @@ static int encoder_encode_impl(x265amd_encoder* e, x265amd_nal** ppNal, uint32_t
     const bool flushing = picIn == nullptr;
     /* The slice-type decisions.  With pictures coming in, whatever a full queue allows.  When the caller flushes, ONE mini-GOP at a time (below): each decision of
      * the lookahead takes as long as a P picture, and the pictures of the first mini-GOP have no reason to wait for the decisions about the last -- a clip shorter than
-     * the lookahead is decided entirely while it is flushed, and its first P picture used to start when the last decision was made (X265AMD_FLUSH_DECIDE_ALL=1: that
-     * form).  The decisions themselves do not depend on when they are made. */
-    static const bool decideAll = getenv("X265AMD_FLUSH_DECIDE_ALL") && atoi(getenv("X265AMD_FLUSH_DECIDE_ALL")) != 0;
+     * the lookahead is decided entirely while it is flushed, and its first P picture used to start when the last decision was made.  The decisions themselves do not depend on
+     * when they are made. */
     auto decide = [e, flushing]() -> int {
         const auto tl1 = std::chrono::steady_clock::now();
         int rc = X265AMD_OK;
-        if (e->lookahead) rc = e->decideLookahead(flushing, flushing && !decideAll ? 1 : 1 << 30);
+        if (e->lookahead) rc = e->decideLookahead(flushing, flushing ? 1 : 1 << 30);
         else e->decideMiniGop(flushing);
         const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tl1).count();
         e->laDecideMs += ms;
-        static const bool timingD = getenv("X265AMD_TIMING") != nullptr;
+        static const bool timingD = xa_env_present("X265AMD_TIMING");
         if (timingD && ms > 0.5) fprintf(stderr, "x265amd: decision: %.1f ms, %d pictures typed, %d still in the lookahead%s\n", ms, (int)e->ready.size(), (int)e->input.size(), flushing ? " (flushing)" : "");
         return rc;
     };
@@ -608,7 +605,7 @@ static int encoder_encode_impl(x265amd_encoder* e, x265amd_nal** ppNal, uint32_t
         return 0;
     };
     if (decide() != X265AMD_OK || admit()) return -1;
-    const bool timing = getenv("X265AMD_TIMING") != nullptr;
+    const bool timing = xa_env_present("X265AMD_TIMING");
     auto start = [e, timing](const PicP& pic) {
         std::shared_future<int> prev = e->lastTask;
         pic->started = true;
@@ -622,7 +619,7 @@ static int encoder_encode_impl(x265amd_encoder* e, x265amd_nal** ppNal, uint32_t
                  * no reference: the row pump does not send it) */
                 if (pic->type == TYPE_B) { if (!e->keepSources()) { xa_scratch_free(pic->dSrc); pic->dSrc = nullptr; } return (int)X265AMD_OK; }
                 std::unique_lock<std::mutex> lk(pic->mu);
-                static const int importWaitS = getenv("X265AMD_IMPORT_WAIT_S") ? atoi(getenv("X265AMD_IMPORT_WAIT_S")) : 300;       /* (debugging a stalled pump: a short wait shows where it stands) */
+                static const int importWaitS = xa_env_int("X265AMD_IMPORT_WAIT_S", 300);       /* (debugging a stalled pump: a short wait shows where it stands) */
                 const bool ok = pic->cv.wait_for(lk, std::chrono::seconds(importWaitS), [&] { return pic->importedRows >= e->ctuH || pic->failed.load(); });
                 if (!ok || pic->failed.load()) { lk.unlock(); pic->fail(); return xa_fail(X265AMD_EHIP, "encoder: a picture coded elsewhere did not arrive"); }
                 lk.unlock();
@@ -642,16 +639,11 @@ static int encoder_encode_impl(x265amd_encoder* e, x265amd_nal** ppNal, uint32_t
     };
     /* Tasks start in coding order while fewer than frameThreads + 1 run.  Coded in parallel, a picture without references does not wait for its turn: nothing it needs
      * comes from another picture, and an I picture takes as long as a dozen of the others -- started when the lookahead hands it over, it is coded beside the pictures
-     * in front of it instead of holding up the ones behind it (X265AMD_EARLY_I=0: in turn).  Output stays in coding order. */
-    static const bool earlyI = !(getenv("X265AMD_EARLY_I") && atoi(getenv("X265AMD_EARLY_I")) == 0);
-    static const int earlyIMax = getenv("X265AMD_EARLY_I_MAX") ? atoi(getenv("X265AMD_EARLY_I_MAX")) : 1 << 20;
-    static const bool earlyP = !(getenv("X265AMD_EARLY_P") && atoi(getenv("X265AMD_EARLY_P")) == 0);
-    static const bool earlyPAlways = getenv("X265AMD_EARLY_P") && atoi(getenv("X265AMD_EARLY_P")) == 2;
-    static const bool earlyBref = getenv("X265AMD_EARLY_BREF") && atoi(getenv("X265AMD_EARLY_BREF")) != 0;      /* a referenced B picture is a link of the same chain */
-    static const int earlyPMax = getenv("X265AMD_EARLY_P_MAX") ? atoi(getenv("X265AMD_EARLY_P_MAX")) : 6;
+     * in front of it instead of holding up the ones behind it.  Output stays in coding order. */
+    const int earlyPMax = 6;
     /* (measured, profiles/r05_early_b_sweep.txt: 2160p clips 15-22 % shorter with 12, 8-bit, Main 10 and --preset slow alike; the 1080p clips unchanged or -- the
      * sixty-frame clip with its two scene cuts -- 15 % longer: there an I picture behind a scene cut shares the device with a dozen pictures more.  So: by size) */
-    const int earlyBMax = getenv("X265AMD_EARLY_B_MAX") ? atoi(getenv("X265AMD_EARLY_B_MAX")) : (e->ctuH > 24 ? 12 : 0);
+    const int earlyBMax = e->ctuH > 24 ? 12 : 0;
     auto launch = [&]() {
     const bool headLong = !e->inflight.empty() && (e->inflight.front()->type == TYPE_IDR || e->inflight.front()->type == TYPE_I) && e->inflight.front()->started &&
                           e->inflight.front()->done.wait_for(std::chrono::seconds(0)) != std::future_status::ready;
@@ -660,39 +652,24 @@ static int encoder_encode_impl(x265amd_encoder* e, x265amd_nal** ppNal, uint32_t
         if (q->started) continue;
         /* the first picture in coding order always runs: it is the one collected next, whatever started ahead of its turn */
         if (e->running <= e->frameThreads || q == e->inflight.front()) { start(q); if (e->frameThreads <= 1) q->done.wait(); continue; }
-        if (!(e->frameParallel && earlyI)) break;
-        if (q->type == TYPE_IDR || q->type == TYPE_I)
-        {
-            /* (X265AMD_EARLY_I_MAX: no more of them at once than this -- an experiment of round 5's end: while P pictures started ahead of their turn all the time, a limit
-             * of one helped a long 2160p clip; with the P pictures held to their turn outside an I picture's time it does not, and there is none.  profiles/r05_sched_sweep.txt) */
-            int runningI = 0;
-            for (auto& o : e->inflight)
-                if (o->started && (o->type == TYPE_IDR || o->type == TYPE_I) && o->done.wait_for(std::chrono::seconds(0)) != std::future_status::ready) runningI++;
-            if (runningI < earlyIMax) start(q);
-        }
+        if (!e->frameParallel) break;
+        /* (however many I pictures run already: a limit of one helped a long 2160p clip only while P pictures started ahead of their turn all the time.  profiles/r05_sched_sweep.txt) */
+        if (q->type == TYPE_IDR || q->type == TYPE_I) start(q);
         /* The P pictures are the chain every other picture hangs on (each follows its reference by a few CTU rows, the B pictures between two of them follow both): a P
          * picture held back until the B pictures in front of it have been collected starts with nothing to trail and takes its full latency, so it starts when the
-         * lookahead hands it over, too (every picture it references is in front of it in coding order and therefore started; X265AMD_EARLY_P=0: in turn). */
-        /* (round 5's end: like the B pictures below, only while a running I picture holds the head of the coding order -- X265AMD_EARLY_P=2: always, as round 4 had it.
+         * lookahead hands it over, too (every picture it references is in front of it in coding order and therefore started). */
+        /* (round 5's end: like the B pictures below, only while a running I picture holds the head of the coding order.
          * With P pictures ahead of their turn ALL the time a long clip stood at 52 frames/s where it reaches 100 without: the pictures far ahead held the places
          * and the queues that the pictures collected next were waiting for; profiles/r05_sched_sweep.txt) */
-        else if (earlyP && (headLong || earlyPAlways) && (q->type == TYPE_P || (earlyBref && q->type == TYPE_BREF)) && e->running <= e->frameThreads + earlyPMax) start(q);
+        else if (headLong && q->type == TYPE_P && e->running <= e->frameThreads + earlyPMax) start(q);
         /* The B pictures, too (round 5), while an I picture that still runs holds the head of the coding order: `running` counts every picture that trails it and is not
          * collected yet (collection is in coding order), and the B pictures of the mini-GOPs whose P pictures ran already waited for the I picture's END although their
          * references were rows ahead of them -- at 2160p a third of a twenty-frame clip, at --preset slow more.  How many pictures run side by side changes nothing in
-         * what they code (the vertical reach of the vectors follows from the parameter frameNumThreads, not from this count): up to X265AMD_EARLY_B_MAX more than the
+         * what they code (the vertical reach of the vectors follows from the parameter frameNumThreads, not from this count): up to earlyBMax more than the
          * parameter (0: in turn).  Only then, and only for large pictures (see earlyBMax above). */
         else if (earlyBMax > 0 && headLong && e->running <= e->frameThreads + earlyBMax) start(q);
     }
     };
-    static const bool holdUntilFlush = getenv("X265AMD_HOLD_UNTIL_FLUSH") != nullptr;      /* an experiment: no picture starts before the caller flushes (what the clip costs when every decision is made beforehand) */
-    if (holdUntilFlush)
-    {
-        if (!flushing) return 0;
-        while (!e->input.empty()) { const size_t before = e->input.size(); if (decide() != X265AMD_OK || admit()) return -1; if (e->input.size() >= before) break; }
-        static bool said = false;
-        if (!said) { said = true; fprintf(stderr, "x265amd: every decision made %.1f ms after the encoder's first picture came in; the pictures start now\n", Pic::pubClockMs() - e->firstInMs); }
-    }
     launch();
     /* flushing: the next mini-GOP is decided while the picture the caller will get next is still being coded */
     while (flushing && !e->input.empty())
@@ -721,7 +698,7 @@ static int encoder_encode_impl(x265amd_encoder* e, x265amd_nal** ppNal, uint32_t
         while (!e->byCoding.empty() && e->byCoding.begin()->first + 8 < e->collectedCoding) e->byCoding.erase(e->byCoding.begin());
     }
     if (rc) { xa_fail(rc, "encoder_encode: a frame task failed"); return -1; }
-    if (const char* dumpPath = getenv("X265AMD_RC_DUMP"))
+    if (const char* dumpPath = xa_env_str("X265AMD_RC_DUMP"))
     {
         /* debugging aid: the picture's record in the layout of oracle/ref_rc_dump.cpp (the reference's decisions for the same picture), appended to the file named */
         if (FILE* f = fopen(dumpPath, "ab"))

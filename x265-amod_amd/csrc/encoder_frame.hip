@@ -318,7 +318,7 @@ static int gateCtuWait(void* ctx, int row, int col)         /* blocking: the tas
     RowGate& g = *(RowGate*)ctx;
     const x265amd_encoder& e = *g.e;
     const int need = gateNeed(e, col), r0 = std::max(0, row - 2), r1 = std::min(e.ctuH - 1, row + 1);
-    static const bool pubLog = getenv("X265AMD_PUB_LOG") != nullptr;
+    static const bool pubLog = xa_env_present("X265AMD_PUB_LOG");
     for (Pic* q : g.refs)
         for (int r = r1; r >= r0; r--)
         {
@@ -479,7 +479,7 @@ int x265amd_encoder::filterRows(Pic& pic, const x265amd_slice_info& si, const x2
         pic.publish(k, W);
         return X265AMD_OK;
     };
-    static const bool timing = getenv("X265AMD_TIMING") != nullptr;
+    static const bool timing = xa_env_present("X265AMD_TIMING");
     double tPh[6] = { 0, 0, 0, 0, 0, 0 };
     auto tLast = std::chrono::steady_clock::now();
     auto stamp = [&](int k) { if (!timing) return; const auto n = std::chrono::steady_clock::now(); tPh[k] += std::chrono::duration<double, std::milli>(n - tLast).count(); tLast = n; };
@@ -537,9 +537,8 @@ int x265amd_encoder::filterRows(Pic& pic, const x265amd_slice_info& si, const x2
  * nr_throttled; a dozen milliseconds each time, in the middle of the encode).  An event, a short poll for the common case (the work is a few kernels), then naps. */
 static hipError_t streamWaitPolite(hipStream_t st, hipEvent_t ev)
 {
-    static const bool off = getenv("X265AMD_FILTER_SPIN") && atoi(getenv("X265AMD_FILTER_SPIN")) != 0;
-    static const int spinUs = getenv("X265AMD_FILTER_SPIN_US") ? atoi(getenv("X265AMD_FILTER_SPIN_US")) : 30;
-    if (off || !ev) return hipStreamSynchronize(st);
+    const int spinUs = 30;
+    if (!ev) return hipStreamSynchronize(st);
     hipError_t e = hipEventRecord(ev, st);
     if (e != hipSuccess) return e;
     const auto t0 = std::chrono::steady_clock::now();
@@ -578,17 +577,14 @@ int x265amd_encoder::filterRowsCols(Pic& pic, const x265amd_slice_info& si, cons
     struct EventGuard { hipEvent_t e; ~EventGuard() { if (e) (void)hipEventDestroy(e); } } evGuard{ ev };
     const bool sao = p.bEnableSAO != 0, dbl = p.bEnableLoopFilter != 0;
     const size_t nUnits = (size_t)w4 * h4, ctuStat = (size_t)3 * 5 * 32, nstat = (size_t)nctu * ctuStat;
-    /* device: deblocking records, SAO parameters.  Pinned host memory the device reads / writes in place (no staging copies, no synchronisation to free a
-     * staging buffer): the records as the host derives them (copied to the device in stream order), the statistics as the kernel stores them, the parameters as
-     * decided (copied in stream order). */
-    struct Scratch { void* p = nullptr; ~Scratch() { xa_scratch_free(p); } } dDb, dPar;
+    /* deblocking records, SAO statistics and parameters: mapped memory the device reads / writes in place (no staging copies, no synchronisation to free a
+     * staging buffer): the records as the host derives them, the statistics as the kernel stores them, the parameters as decided. */
     XaMapped hDb, hPar; XaMappedOut hCnt, hOrg;
-    if (dbl && (xa_scratch_alloc(&dDb.p, sizeof(x265amd_deblock_unit) * nUnits) != hipSuccess || hDb.alloc(sizeof(x265amd_deblock_unit) * nUnits) != hipSuccess))
+    if (dbl && hDb.alloc(sizeof(x265amd_deblock_unit) * nUnits) != hipSuccess)
         return xa_fail(X265AMD_EHIP, "encoder: device allocation");
     if (sao)
     {
-        if (xa_scratch_alloc(&dPar.p, sizeof(x265amd_sao_ctu) * nctu) != hipSuccess || hPar.alloc(sizeof(x265amd_sao_ctu) * nctu) != hipSuccess ||
-            hCnt.alloc(nstat * 4) != hipSuccess || hOrg.alloc(nstat * 4) != hipSuccess)
+        if (hPar.alloc(sizeof(x265amd_sao_ctu) * nctu) != hipSuccess || hCnt.alloc(nstat * 4) != hipSuccess || hOrg.alloc(nstat * 4) != hipSuccess)
             return xa_fail(X265AMD_EHIP, "encoder: device allocation");
         saoFlags[0] = saoFlags[1] = 1;          /* SAO::startSlice: never switched off when pictures are coded in parallel (sao.cpp:264) */
     }
@@ -599,17 +595,13 @@ int x265amd_encoder::filterRowsCols(Pic& pic, const x265amd_slice_info& si, cons
     const uint64_t srcP[3] = { planeAddr(pic.dSrc, 0), planeAddr(pic.dSrc, 1), planeAddr(pic.dSrc, 2) };
     pixel* fin = sao ? pic.dFin : pic.dRec;
     const uint64_t finP[3] = { planeAddr(fin, 0), planeAddr(fin, 1), planeAddr(fin, 2) };
-    static const bool timing = getenv("X265AMD_TIMING") != nullptr;
+    static const bool timing = xa_env_present("X265AMD_TIMING");
     double tWait = 0, tWork = 0; int numUnits = 0, numSweeps = 0;
     auto tLast = std::chrono::steady_clock::now();
     auto lap = [&](double& acc) { if (!timing) return; const auto n = std::chrono::steady_clock::now(); acc += std::chrono::duration<double, std::milli>(n - tLast).count(); tLast = n; };
     struct Report { const bool& on; double& w; double& k; int& n; int& sw; int poc; ~Report() { if (on) fprintf(stderr, "x265amd: filter units of poc %d: %d units in %d sweeps, %.1f ms waiting for the analysis, %.1f ms filtering\n", poc, n, sw, w, k); } } report{ timing, tWait, tWork, numUnits, numSweeps, pic.poc };
     /* a picture nobody references is waited for by nobody: whole rows */
-    /* the offsets' parameters are read by the kernel where the host wrote them (mapped memory: device memory behind the BAR unless X265AMD_PUSH_RECORDS=0 put the pools
-     * into host memory, where a read per sample would cross PCIe: then they are copied as before) */
-    static const bool parCopy = (getenv("X265AMD_SAO_PARAMS_COPY") && atoi(getenv("X265AMD_SAO_PARAMS_COPY")) != 0) || (getenv("X265AMD_PUSH_RECORDS") && atoi(getenv("X265AMD_PUSH_RECORDS")) == 0);
-    static const int minChunkEnv = getenv("X265AMD_FILTER_CHUNK") ? atoi(getenv("X265AMD_FILTER_CHUNK")) : 0;
-    const int minChunk = pic.type == TYPE_B ? ctuW : (minChunkEnv > 0 ? minChunkEnv : 2);
+    const int minChunk = pic.type == TYPE_B ? ctuW : 2;
     /* the last rows are where a chain of pictures waits for each other (they finish last, and cut CTUs make the last row the slowest): every CTU of them at once */
     const int minChunkLast = pic.type != TYPE_B ? 1 : minChunk;
     /* which chunks a snapshot of the analysis allows, in which order, and what is final behind them: x265amd_filter_plan (host/filter_plan.cpp) */
@@ -622,7 +614,7 @@ int x265amd_encoder::filterRowsCols(Pic& pic, const x265amd_slice_info& si, cons
     auto finishCols = [&](const x265amd_filter_finish& f) -> int {
         if (sao)
         {
-            int r = x265amd_sao_apply_rows_cols(st, recP, finP, stride, cstride, W, H, parCopy ? (const x265amd_sao_ctu*)dPar.p : (const x265amd_sao_ctu*)hPar.p, f.row, f.row + 1, f.x_begin, f.x_end);
+            int r = x265amd_sao_apply_rows_cols(st, recP, finP, stride, cstride, W, H, (const x265amd_sao_ctu*)hPar.p, f.row, f.row + 1, f.x_begin, f.x_end);
             if (r != X265AMD_OK) return r;
         }
         return xa_extend_border_band_420(st, fin + org[0], fin + org[1], fin + org[2], stride, cstride, W, H, marginX, marginY, f.y_begin, f.y_end, f.x_begin, f.x_end, f.x_begin == 0, f.x_end == W);
@@ -631,8 +623,8 @@ int x265amd_encoder::filterRowsCols(Pic& pic, const x265amd_slice_info& si, cons
      * the row ABOVE -- as soon as the row itself is analysed (nothing of this touches the row's last line, which the row below still reads unfiltered); the row above can
      * then be offset, extended and published: one CTU row earlier than when everything waited for the row below.  FULL: the other vertical edges, the inner horizontal
      * edges, the statistics and the decisions, when the row below is analysed (FrameEncoder::m_filterRowDelay).  Vertical edges are decided per four lines and touch only
-     * their own lines, the top horizontal edge touches lines 0-2: the samples are those of the reference's order (X265AMD_FILTER_EARLY_TOP=0: both steps together). */
-    static const bool earlyTop = !(getenv("X265AMD_FILTER_EARLY_TOP") && atoi(getenv("X265AMD_FILTER_EARLY_TOP")) == 0);
+     * their own lines, the top horizontal edge touches lines 0-2: the samples are those of the reference's order. */
+    const int earlyTop = 1;
     for (;;)
     {
         {
@@ -654,7 +646,6 @@ int x265amd_encoder::filterRowsCols(Pic& pic, const x265amd_slice_info& si, cons
         int numSteps = 0, numFinish = 0;
         if (x265amd_filter_plan(W, H, a.data(), doneTop.data(), doneFull.data(), pubX.data(), minChunk, minChunkLast, earlyTop, steps.data(), &numSteps, finish.data(), &numFinish) != X265AMD_OK)
         { rc = xa_fail(X265AMD_EINVAL, "encoder: filter plan"); break; }
-        static const bool dbCopy = getenv("X265AMD_DEBLOCK_UNITS_COPY") && atoi(getenv("X265AMD_DEBLOCK_UNITS_COPY")) != 0;
         bool anyFull = false;
         for (int i = 0; i < numSteps && rc == X265AMD_OK; i++)
         {
@@ -666,11 +657,7 @@ int x265amd_encoder::filterRowsCols(Pic& pic, const x265amd_slice_info& si, cons
                 rc = x265amd_deblock_units_rect(&si, &info, pic.units.data(), pic.motion.data(), dbu, s.y4_begin, s.rec_y4_end, s.rec_x4_begin, s.rec_x4_end);
                 if (rc != X265AMD_OK) break;
                 _mm_sfence();       /* the records went through the write-combining BAR mapping: out of this core's buffers before the launch that reads them */
-                const size_t first = (size_t)s.y4_begin * w4 + s.rec_x4_begin;
-                if (dbCopy && hipMemcpy2DAsync((x265amd_deblock_unit*)dDb.p + first, sizeof(x265amd_deblock_unit) * w4, dbu + first, sizeof(x265amd_deblock_unit) * w4,
-                                     sizeof(x265amd_deblock_unit) * (size_t)(s.rec_x4_end - s.rec_x4_begin), (size_t)(s.rec_y4_end - s.y4_begin), hipMemcpyHostToDevice, st) != hipSuccess)
-                { rc = xa_fail(X265AMD_EHIP, "encoder: deblock upload"); break; }
-                rc = x265amd_deblock_rows_cols(st, recY, recU, recV, stride, cstride, W, H, dbCopy ? (const x265amd_deblock_unit*)dDb.p : dbu, p.deblockingFilterBetaOffset, p.deblockingFilterTCOffset, 0, 0, 0, 3, s.y4_begin, s.y4_end, s.col_begin, s.col_end);
+                rc = x265amd_deblock_rows_cols(st, recY, recU, recV, stride, cstride, W, H, dbu, p.deblockingFilterBetaOffset, p.deblockingFilterTCOffset, 0, 0, 0, 3, s.y4_begin, s.y4_end, s.col_begin, s.col_end);
                 if (rc != X265AMD_OK) break;
             }
             else
@@ -678,7 +665,7 @@ int x265amd_encoder::filterRowsCols(Pic& pic, const x265amd_slice_info& si, cons
                 anyFull = true;
                 if (dbl && s.y4_end > s.y4_begin)
                 {
-                    rc = x265amd_deblock_rows_cols(st, recY, recU, recV, stride, cstride, W, H, dbCopy ? (const x265amd_deblock_unit*)dDb.p : dbu, p.deblockingFilterBetaOffset, p.deblockingFilterTCOffset, 0, 0, 0, 3, s.y4_begin, s.y4_end, s.col_begin, s.col_end);
+                    rc = x265amd_deblock_rows_cols(st, recY, recU, recV, stride, cstride, W, H, dbu, p.deblockingFilterBetaOffset, p.deblockingFilterTCOffset, 0, 0, 0, 3, s.y4_begin, s.y4_end, s.col_begin, s.col_end);
                     if (rc != X265AMD_OK) break;
                 }
                 if (sao)
@@ -706,8 +693,6 @@ int x265amd_encoder::filterRowsCols(Pic& pic, const x265amd_slice_info& si, cons
                 const size_t off = (size_t)u.row * ctuW + u.col_begin, n = (size_t)(u.col_end - u.col_begin);
                 memcpy((x265amd_sao_ctu*)hPar.p + off, sparams.data() + off, sizeof(x265amd_sao_ctu) * n);
                 _mm_sfence();               /* as for the deblocking records above */
-                if (parCopy && hipMemcpyAsync((x265amd_sao_ctu*)dPar.p + off, (const x265amd_sao_ctu*)hPar.p + off, sizeof(x265amd_sao_ctu) * n, hipMemcpyHostToDevice, st) != hipSuccess)
-                { rc = xa_fail(X265AMD_EHIP, "encoder: sao upload"); break; }
             }
             if (rc != X265AMD_OK) break;
         }
@@ -764,15 +749,12 @@ int x265amd_encoder::runFrameParallel(const PicP& picp)
     int32_t saoFlags[2] = { 0, 0 };
     int filterRc = X265AMD_OK;
     /* by columns when there is something to filter and the rows run as a wavefront; the row-by-row form otherwise */
-    static const bool colsOff = getenv("X265AMD_FILTER_COLS") && atoi(getenv("X265AMD_FILTER_COLS")) == 0;
+    static const bool colsOff = !xa_env_on("X265AMD_FILTER_COLS");
     const bool byCols = !colsOff && p.bEnableWavefront && (p.bEnableLoopFilter || p.bEnableSAO) && ctuH > 1 && ctuW > 1;
     std::thread filters([&, byCols] { xa_thread_device(); filterRc = byCols ? filterRowsCols(pic, fc.si, fc.info, sparams, saoFlags) : filterRows(pic, fc.si, fc.info, sparams, saoFlags); if (filterRc) pic.fail();
                                       cpuFilterNs += thread_cpu_ns(); });
-    /* the rows' priority among the row tasks of all pictures in flight: the picture's place in coding order -- an I picture some places earlier (X265AMD_I_BOOST): its
-     * chain of 8x8 CUs is the longest thing in flight, nothing it needs comes from another picture, and the pictures behind the scene cut wait for it */
-    static const uint64_t iBoost = getenv("X265AMD_I_BOOST") ? (uint64_t)atoi(getenv("X265AMD_I_BOOST")) : 0;
-    const bool isI = pic.type == TYPE_IDR || pic.type == TYPE_I;
-    const uint64_t rowOrder = isI ? (pic.codingOrder + 1 > iBoost ? pic.codingOrder + 1 - iBoost : 1) : pic.codingOrder + 1;
+    /* the rows' priority among the row tasks of all pictures in flight: the picture's place in coding order */
+    const uint64_t rowOrder = pic.codingOrder + 1;
     const XaRowHooks hooks{ &gate, gateRowReady, gateBeforeRow, gateAfterRow, gateCtuWait, gateBeforeCtu, gateAfterCtu, gateRefWait, rowOrder, gateCtuReach };
     XaTuRecs tuRecs = { nullptr, { nullptr, nullptr } };
     if (p.limitTU >= 3)

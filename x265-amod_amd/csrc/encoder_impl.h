@@ -153,7 +153,7 @@ struct Pic
     void publish(int row, int x)
     {
         std::atomic_thread_fence(std::memory_order_release); *finalX[row] = (uint64_t)x;
-        static const bool pubLog = getenv("X265AMD_PUB_LOG") != nullptr;      /* with the gate's waits (gateCtuWait): who waited for which publication, and when it came */
+        static const bool pubLog = xa_env_present("X265AMD_PUB_LOG");      /* with the gate's waits (gateCtuWait): who waited for which publication, and when it came */
         if (pubLog) fprintf(stderr, "x265amd pub: poc %d row %d x %d at %.2f\n", poc, row, x, pubClockMs());
     }
     static double pubClockMs() { return fmod(std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(), 1e6); }       /* the clock of X265AMD_CTU_LOG */
@@ -200,7 +200,6 @@ struct x265amd_encoder
     std::shared_future<int> lastTask;                   /* the previous picture's task: in-loop filters and SAO run in coding order */
     int frameThreads = 1;
     double uploadMs = 0;        /* X265AMD_TIMING: the callers' time in uploadPicture */
-    double firstInMs = -1;      /* X265AMD_HOLD_UNTIL_FLUSH: when the first picture came in (Pic::pubClockMs) */
     std::atomic<uint64_t> cpuPictureNs{ 0 }, cpuFilterNs{ 0 };      /* X265AMD_TIMING: CPU time of the picture threads and the filter threads (CLOCK_THREAD_CPUTIME_ID) */
     bool frameParallel = false;                         /* param.frameNumThreads > 1: the reference's frame-parallel rules (search.cpp:77-92, sao.cpp:264) */
     int refLagRows = 0;                                 /* FrameEncoder::m_refLagRows (frameencoder.cpp:170-175) */
@@ -218,7 +217,7 @@ struct x265amd_encoder
         for (auto& q : inflight) if (q->done.valid()) q->done.wait();
         laFieldsFree();
         if (uploadBuf) (void)hipHostFree(uploadBuf);
-        if (getenv("X265AMD_TIMING") && lookahead)
+        if (xa_env_present("X265AMD_TIMING") && lookahead)
         {
             fprintf(stderr, "x265amd: input: %.1f ms in uploads; cpu of the picture threads %.1f ms, of the filter threads %.1f ms\n", uploadMs, cpuPictureNs.load() / 1e6, cpuFilterNs.load() / 1e6);
             fprintf(stderr, "x265amd: lookahead: %.1f ms in lowres planes + intra costs, %.1f ms in the slice-type decision (%llu estimates, %llu motion searches; %llu batches %.1f ms, %llu single estimates %.1f ms)\n", laInitMs, laDecideMs,

@@ -20,7 +20,7 @@ int x265amd_encoder::lowresInit(Pic& pic)
     rc = x265amd_lowres_intra_costs(laStream, planes[0], lowStride, lowCuW, lowCuH, lambda, pic.dIntraCost, dMode);
     if (rc != X265AMD_OK) return rc;
     /* the picture's sums for the weight analysis are measured in front of the one wait of this function */
-    static const char* const dbgWp = getenv("X265AMD_WP_DEBUG");          /* debugging aid: letters s / l / p switch the sums, the lookahead's analysis, the slice's analysis off */
+    static const char* const dbgWp = xa_env_str("X265AMD_WP_DEBUG");          /* debugging aid: letters s / l / p switch the sums, the lookahead's analysis, the slice's analysis off */
     const bool sums = (p.bEnableWeightedPred || p.bEnableWeightedBiPred) && !(dbgWp && strchr(dbgWp, 's'));
     if (sums && !aqOn)
     {
@@ -338,7 +338,7 @@ int x265amd_encoder::sliceWeights(Pic& pic)
         for (int plane = 0; plane < 3; plane++) pic.weighted |= weights[plane].present != 0;
     }
     pic.lumaDenom = pic.wp[0][0][0].denom; pic.chromaDenom = pic.wp[0][0][1].denom;         /* what pred_weight_table() codes once: the first reference's (entropy.cpp:1376-1387) */
-    const bool wpLog = getenv("X265AMD_WP_LOG") != nullptr;         /* (read per picture: a test switches it on for one encode) */
+    const bool wpLog = xa_env_present("X265AMD_WP_LOG");         /* (read per picture: a test switches it on for one encode) */
     if (wpLog && pic.weighted)
     {
         /* the reference's --log-level full line */
@@ -478,7 +478,7 @@ int x265amd_encoder::frameCostMany(std::vector<CostJob>& jobs)
         /* (an estimate made ahead of its time reads and fills the fields made ahead of their time as well as the picture's own) */
         const bool have0 = !fenc.lowMvs[j.d0].empty() || (j.spec && !fenc.specMvs[j.d0].empty()), have1 = j.d1 > 0 && (!fenc.lowMvs1[j.d1].empty() || (j.spec && !fenc.specMvs1[j.d1].empty()));
         j.search0 = !have0; j.search1 = j.d1 > 0 && !have1;
-        static const char* const dbgWp = getenv("X265AMD_WP_DEBUG");
+        static const char* const dbgWp = xa_env_str("X265AMD_WP_DEBUG");
         if (p.bEnableWeightedPred && j.search0 && !(dbgWp && strchr(dbgWp, 'l')) && lookaheadWeightGuess(fenc, *j.ref0, lw[k]))
         {
             x265amd_weight_cost_job w;

@@ -62,7 +62,7 @@ int x265amd_encoder::prepare(const PicP& picp)
             statPictures[stype == 1 ? 1 : 2]++; statReferences += seen.size();
         }
     }
-    static const char* const dbgWp = getenv("X265AMD_WP_DEBUG");
+    static const char* const dbgWp = xa_env_str("X265AMD_WP_DEBUG");
     memset(pic.wp, 0, sizeof(pic.wp)); pic.weighted = false;
     if (((p.bEnableWeightedPred && stype == 1) || (p.bEnableWeightedBiPred && stype == 0)) && !(dbgWp && strchr(dbgWp, 'p')))
     {
@@ -88,7 +88,7 @@ int x265amd_encoder::prepare(const PicP& picp)
         if (qp < 0) return xa_fail(X265AMD_EINVAL, "encoder_encode: rate control");
         pic.sliceQp = std::min(qp, 51);             /* FrameEncoder::compressFrame clips the slice QP to the range the syntax carries (frameencoder.cpp:612) */
         if (useDqp) cuQpTable(pic);
-        static const bool rcLog = getenv("X265AMD_RC_LOG") != nullptr;
+        static const bool rcLog = xa_env_present("X265AMD_RC_LOG");
         if (rcLog) fprintf(stderr, "x265amd rc: poc %d type %d qp %d avgQpRc %.9f satd %lld scenecut %d\n", pic.poc, pic.type, pic.sliceQp, pic.avgQpRc, (long long)f.satd_cost, (int)pic.bScenecut);
     }
     else

@@ -42,11 +42,7 @@ __global__ __launch_bounds__(64 * MEASURE_WG_WAVES) void k_cu_measure_wg(const C
     const CuMeasureJob j = xa_ld_record(jobs + blockIdx.x);
     block_cu_measure_job(j, out + blockIdx.x, lds, threadIdx.x, 64 * MEASURE_WG_WAVES);
 }
-static bool measure_use_wg(int n)
-{
-    static const int wgMax = getenv("X265AMD_MEASURE_WG_MAX") ? atoi(getenv("X265AMD_MEASURE_WG_MAX")) : 64;
-    return n <= wgMax;
-}
+static bool measure_use_wg(int n) { return n <= 64; }
 
 /* ---------------- host: the reference's walk ---------------- */
 namespace {
@@ -1011,51 +1007,47 @@ static int inter_residual_rd_impl(void* stream_, const x265amd_slice_info* si, c
         };
         /* a node's three units as two commands and one wait: both tables (luma, chroma) by two wavefronts of one est_bit command, the three chains by three wavefronts of
          * one tu_chain_rdoq command -- the job records are copied side by side for that (they lie apart in the plan), the results go back to their places */
-        static const bool together = !(getenv("X265AMD_RDOQ_TOGETHER") && atoi(getenv("X265AMD_RDOQ_TOGETHER")) == 0);
-        if (together)
-        {
-            XA_HIP_CHECK(mNodeCtx.alloc(X265AMD_CTX_STRIDE)); XA_HIP_CHECK(mNodeEst.alloc(2 * sizeof(x265amd_est_job))); XA_HIP_CHECK(mNodeRq.alloc(3 * sizeof(x265amd_tu_rdoq)));
-            XA_HIP_CHECK(mNodeJobs.alloc(3 * sizeof(x265amd_tu_job))); XA_HIP_CHECK(mNodeRes.alloc(3 * sizeof(x265amd_tu_result)));
-            XA_HIP_CHECK(dEst2.alloc(2 * sizeof(x265amd_est_bits)));
-            XA_HIP_CHECK(xa_fill_async(stream_, dEst2.p, 0, 2 * sizeof(x265amd_est_bits)));
-            demandFn.node = [&](int i, const uint8_t* ctx, int jy, int ju, int jv, int log2TrSize, int log2TrSizeC, int tuDepth) -> int {
-                const x265amd_tu_job* jobs = (const x265amd_tu_job*)mJobs.p;
-                const int idx[3] = { jy, ju, jv };
-                memcpy(mNodeCtx.p, ctx, X265AMD_CTX_COUNT);
-                x265amd_est_job* ej = (x265amd_est_job*)mNodeEst.p;
-                memset(ej, 0, 2 * sizeof(*ej));
-                char* tables = (char*)dEst2.p;
-                for (int t = 0; t < 2; t++)
-                {
-                    ej[t].ctx = (uint64_t)(uintptr_t)mNodeCtx.p; ej[t].est = (uint64_t)(uintptr_t)(tables + (size_t)t * sizeof(x265amd_est_bits));
-                    ej[t].log2_tr_size = (uint8_t)(t ? log2TrSizeC : log2TrSize); ej[t].is_luma = t ? 0 : 1;
-                }
-                int r = x265amd_est_bit(stream_, ej, 2);
-                if (r != X265AMD_OK) return r;
-                x265amd_tu_job* nj = (x265amd_tu_job*)mNodeJobs.p;
-                x265amd_tu_rdoq* rq = (x265amd_tu_rdoq*)mNodeRq.p;
-                memset(rq, 0, 3 * sizeof(*rq));
-                for (int k = 0; k < 3; k++)
-                {
-                    nj[k] = jobs[idx[k]];
-                    rq[k].est_bits = (uint64_t)(uintptr_t)(tables + (size_t)(k ? 1 : 0) * sizeof(x265amd_est_bits));
-                    x265amd_rdoq_lambda(nj[k].qp_scaled, &rq[k].lambda2, &rq[k].lambda);
-                    rq[k].psy_rdoq_scale = rp->psy_rdoq_scale; rq[k].rdoq_level = (uint8_t)rp->rdoq_level; rq[k].tu_depth = (uint8_t)tuDepth;
-                }
-                r = x265amd_tu_chain_rdoq(stream_, nj, rq, 3, (x265amd_tu_result*)mNodeRes.p);
-                if (r != X265AMD_OK) return r;
-                for (int k = 0; k < 3; k++)
-                {
-                    const size_t nCoeff = (size_t)1 << (2 * nj[k].log2_tr_size);
-                    const size_t off = (size_t)(nj[k].coeff - (uint64_t)(uintptr_t)scratch);
-                    char* dst = (char*)mLevels.p + (size_t)RD_SCRATCH_ELEMS * 2 * i + (off - perCuBytes * i);
-                    if (xa_copy_async(stream_, dst, (const void*)(uintptr_t)nj[k].coeff, nCoeff * 2, hipMemcpyDeviceToHost) != hipSuccess) return xa_fail(X265AMD_EHIP, "inter_residual_rd: RDOQ node");
-                }
-                if (xa_stream_sync(stream_) != hipSuccess) return xa_fail(X265AMD_EHIP, "inter_residual_rd: RDOQ node");
-                for (int k = 0; k < 3; k++) ((x265amd_tu_result*)mRes.p)[idx[k]] = ((const x265amd_tu_result*)mNodeRes.p)[k];
-                return X265AMD_OK;
-            };
-        }
+        XA_HIP_CHECK(mNodeCtx.alloc(X265AMD_CTX_STRIDE)); XA_HIP_CHECK(mNodeEst.alloc(2 * sizeof(x265amd_est_job))); XA_HIP_CHECK(mNodeRq.alloc(3 * sizeof(x265amd_tu_rdoq)));
+        XA_HIP_CHECK(mNodeJobs.alloc(3 * sizeof(x265amd_tu_job))); XA_HIP_CHECK(mNodeRes.alloc(3 * sizeof(x265amd_tu_result)));
+        XA_HIP_CHECK(dEst2.alloc(2 * sizeof(x265amd_est_bits)));
+        XA_HIP_CHECK(xa_fill_async(stream_, dEst2.p, 0, 2 * sizeof(x265amd_est_bits)));
+        demandFn.node = [&](int i, const uint8_t* ctx, int jy, int ju, int jv, int log2TrSize, int log2TrSizeC, int tuDepth) -> int {
+            const x265amd_tu_job* jobs = (const x265amd_tu_job*)mJobs.p;
+            const int idx[3] = { jy, ju, jv };
+            memcpy(mNodeCtx.p, ctx, X265AMD_CTX_COUNT);
+            x265amd_est_job* ej = (x265amd_est_job*)mNodeEst.p;
+            memset(ej, 0, 2 * sizeof(*ej));
+            char* tables = (char*)dEst2.p;
+            for (int t = 0; t < 2; t++)
+            {
+                ej[t].ctx = (uint64_t)(uintptr_t)mNodeCtx.p; ej[t].est = (uint64_t)(uintptr_t)(tables + (size_t)t * sizeof(x265amd_est_bits));
+                ej[t].log2_tr_size = (uint8_t)(t ? log2TrSizeC : log2TrSize); ej[t].is_luma = t ? 0 : 1;
+            }
+            int r = x265amd_est_bit(stream_, ej, 2);
+            if (r != X265AMD_OK) return r;
+            x265amd_tu_job* nj = (x265amd_tu_job*)mNodeJobs.p;
+            x265amd_tu_rdoq* rq = (x265amd_tu_rdoq*)mNodeRq.p;
+            memset(rq, 0, 3 * sizeof(*rq));
+            for (int k = 0; k < 3; k++)
+            {
+                nj[k] = jobs[idx[k]];
+                rq[k].est_bits = (uint64_t)(uintptr_t)(tables + (size_t)(k ? 1 : 0) * sizeof(x265amd_est_bits));
+                x265amd_rdoq_lambda(nj[k].qp_scaled, &rq[k].lambda2, &rq[k].lambda);
+                rq[k].psy_rdoq_scale = rp->psy_rdoq_scale; rq[k].rdoq_level = (uint8_t)rp->rdoq_level; rq[k].tu_depth = (uint8_t)tuDepth;
+            }
+            r = x265amd_tu_chain_rdoq(stream_, nj, rq, 3, (x265amd_tu_result*)mNodeRes.p);
+            if (r != X265AMD_OK) return r;
+            for (int k = 0; k < 3; k++)
+            {
+                const size_t nCoeff = (size_t)1 << (2 * nj[k].log2_tr_size);
+                const size_t off = (size_t)(nj[k].coeff - (uint64_t)(uintptr_t)scratch);
+                char* dst = (char*)mLevels.p + (size_t)RD_SCRATCH_ELEMS * 2 * i + (off - perCuBytes * i);
+                if (xa_copy_async(stream_, dst, (const void*)(uintptr_t)nj[k].coeff, nCoeff * 2, hipMemcpyDeviceToHost) != hipSuccess) return xa_fail(X265AMD_EHIP, "inter_residual_rd: RDOQ node");
+            }
+            if (xa_stream_sync(stream_) != hipSuccess) return xa_fail(X265AMD_EHIP, "inter_residual_rd: RDOQ node");
+            for (int k = 0; k < 3; k++) ((x265amd_tu_result*)mRes.p)[idx[k]] = ((const x265amd_tu_result*)mNodeRes.p)[k];
+            return X265AMD_OK;
+        };
     }
     rc = inter_rd_walk_impl(si, rp, units, cus, n, cu_units, (const x265amd_tu_result*)mRes.p, (const int16_t*)mLevels.p, (size_t)RD_SCRATCH_ELEMS * 2, meas, sel.data(), out,
                             coeff_out, rdoq ? &demandFn : nullptr);
@@ -1065,9 +1057,8 @@ static int inter_residual_rd_impl(void* stream_, const x265amd_slice_info* si, c
     for (int i = 0; i < n; i++) mjobs[i].assemble = 1;
     if (lazyAssemble && n == 1 && !rdoq && xa_is_queue(stream_))
     {
-        static const bool composeOn = !(getenv("X265AMD_COMPOSE_MEASURE") && atoi(getenv("X265AMD_COMPOSE_MEASURE")) == 0);
         x265amd_cu_measure mc;
-        if (composeOn && compose_final_measure(si, cus[0], cu_units[0].part_size, (const x265amd_tu_result*)mRes.p, sel.data(), mc))
+        if (compose_final_measure(si, cus[0], cu_units[0].part_size, (const x265amd_tu_result*)mRes.p, sel.data(), mc))
         {
             rc = assemble_async(stream_, mjobs[0], sel.data());
             if (rc != X265AMD_OK) return rc;
@@ -1133,8 +1124,7 @@ static int assemble_async(void* stream_, const CuMeasureJob& job, const uint8_t*
     XA_HIP_CHECK(xa_copy_async(stream_, dSel2.p, sel, RD_SEL_BYTES, hipMemcpyHostToDevice));
     XA_HIP_CHECK(xa_copy_async(stream_, dJob.p, &j, sizeof(j), hipMemcpyHostToDevice));
     { const XaArgsJobs4 qa = { (uint64_t)(uintptr_t)dJob.p, (uint64_t)(uintptr_t)dOut.p, 0, 0, 1 }; hipError_t le;
-      if (measure_use_wg(1)) XA_LAUNCH(le, stream_, XA_OP_CU_MEASURE, 1, qa, k_cu_measure_wg, dim3(1), dim3(64 * MEASURE_WG_WAVES), 0, (const CuMeasureJob*)dJob.p, 1, (x265amd_cu_measure*)dOut.p);
-      else XA_LAUNCH(le, stream_, XA_OP_CU_MEASURE, 1, qa, k_cu_measure, dim3(1), dim3(64), 0, (const CuMeasureJob*)dJob.p, 1, (x265amd_cu_measure*)dOut.p);
+      XA_LAUNCH(le, stream_, XA_OP_CU_MEASURE, 1, qa, k_cu_measure_wg, dim3(1), dim3(64 * MEASURE_WG_WAVES), 0, (const CuMeasureJob*)dJob.p, 1, (x265amd_cu_measure*)dOut.p);
       XA_HIP_CHECK(le); }
     return X265AMD_OK;
 }
@@ -1174,8 +1164,7 @@ int xa_merge_rd(void* stream_, const x265amd_slice_info* si, const x265amd_rd_pa
     x265amd_cu_measure* meas = (x265amd_cu_measure*)mMeas.p;
     fill_measure_jobs(mjobs, cu, 1, h_src, stride, cstride, d_pred, d_recon_skip, tile_bytes, scratch, perCuBytes, (const char*)dSel.p);
     { const XaArgsJobs4 qa = { (uint64_t)(uintptr_t)(mjobs), (uint64_t)(uintptr_t)(meas), 0, 0, 1 }; hipError_t le;
-      if (measure_use_wg(1)) XA_LAUNCH(le, stream_, XA_OP_CU_MEASURE, 1, qa, k_cu_measure_wg, dim3(1), dim3(64 * MEASURE_WG_WAVES), 0, (const CuMeasureJob*)mjobs, 1, meas);
-      else XA_LAUNCH(le, stream_, XA_OP_CU_MEASURE, 1, qa, k_cu_measure, dim3(1), dim3(64), 0, (const CuMeasureJob*)mjobs, 1, meas);
+      XA_LAUNCH(le, stream_, XA_OP_CU_MEASURE, 1, qa, k_cu_measure_wg, dim3(1), dim3(64 * MEASURE_WG_WAVES), 0, (const CuMeasureJob*)mjobs, 1, meas);
       XA_HIP_CHECK(le); }
     xa_phase(XA_PH_RD_PLAN);
     XA_HIP_CHECK(xa_stream_sync(stream_));
@@ -1204,9 +1193,8 @@ int xa_merge_rd(void* stream_, const x265amd_slice_info* si, const x265amd_rd_pa
     mjobs[0].assemble = 1; mjobs[0].recon = d_recon_merge;
     {
         /* one transform size per plane: the final measurement follows from the units' results, the assembly runs without being waited for */
-        static const bool composeOn = !(getenv("X265AMD_COMPOSE_MEASURE") && atoi(getenv("X265AMD_COMPOSE_MEASURE")) == 0);
         x265amd_cu_measure mc;
-        if (composeOn && xa_is_queue(stream_) && compose_final_measure(si, *cu, merge_units[0].part_size, res, sel.data(), mc))
+        if (xa_is_queue(stream_) && compose_final_measure(si, *cu, merge_units[0].part_size, res, sel.data(), mc))
         {
             /* the scratch with the residual blocks must outlive this call: it goes back to the queue's own list and is reused behind the assembly, in order */
             rc = assemble_async(stream_, mjobs[0], sel.data());
@@ -1217,8 +1205,7 @@ int xa_merge_rd(void* stream_, const x265amd_slice_info* si, const x265amd_rd_pa
     }
     memcpy(dSel.p, sel.data(), sel.size());
     { const XaArgsJobs4 qa = { (uint64_t)(uintptr_t)(mjobs), (uint64_t)(uintptr_t)(meas + 1), 0, 0, 1 }; hipError_t le;
-      if (measure_use_wg(1)) XA_LAUNCH(le, stream_, XA_OP_CU_MEASURE, 1, qa, k_cu_measure_wg, dim3(1), dim3(64 * MEASURE_WG_WAVES), 0, (const CuMeasureJob*)mjobs, 1, meas + 1);
-      else XA_LAUNCH(le, stream_, XA_OP_CU_MEASURE, 1, qa, k_cu_measure, dim3(1), dim3(64), 0, (const CuMeasureJob*)mjobs, 1, meas + 1);
+      XA_LAUNCH(le, stream_, XA_OP_CU_MEASURE, 1, qa, k_cu_measure_wg, dim3(1), dim3(64 * MEASURE_WG_WAVES), 0, (const CuMeasureJob*)mjobs, 1, meas + 1);
       XA_HIP_CHECK(le); }
     XA_HIP_CHECK(xa_stream_sync(stream_));
     x265amd_inter_rd_finish(si, rp, cu, 1, meas + 1, out_merge);

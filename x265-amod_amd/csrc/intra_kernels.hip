@@ -38,9 +38,8 @@ extern "C" int x265amd_intra_scan(void* stream, const x265amd_intra_job* d_jobs,
     if (!d_jobs || !d_sa8d) return xa_fail(X265AMD_EINVAL, "x265amd_intra_scan: bad arguments");
     const XaArgsJobs4 qa = { (uint64_t)(uintptr_t)d_jobs, (uint64_t)(uintptr_t)d_sa8d, (uint64_t)(uintptr_t)d_neighbours, 0, n };
     hipError_t e;
-    /* two forms of the same scan: a workgroup per block below X265AMD_SCAN_WG_MAX blocks (default 256), a wavefront per block above */
-    static const int wgMax = getenv("X265AMD_SCAN_WG_MAX") ? atoi(getenv("X265AMD_SCAN_WG_MAX")) : 256;
-    if (n <= wgMax)
+    /* two forms of the same scan: a workgroup per block up to 256 blocks, a wavefront per block above */
+    if (n <= 256)
         XA_LAUNCH(e, stream, XA_OP_INTRA_SCAN, n, qa, k_intra_scan_wg, dim3(n), dim3(64 * IN_WG_WAVES), 0, d_jobs, n, d_sa8d, d_neighbours);
     else
         XA_LAUNCH(e, stream, XA_OP_INTRA_SCAN, n, qa, k_intra_scan, dim3((n + IN_WAVES - 1) / IN_WAVES), dim3(64 * IN_WAVES), 0, d_jobs, n, d_sa8d, d_neighbours);

@@ -49,15 +49,7 @@ inline unsigned zUnit(int ux, int uy)           /* z-order of unit (ux, uy) insi
 /* The device-side records of a chain of 8x8 CUs (four x265amd_intra_peer + one x265amd_intra_chain) come from a list of their own, not from the pools: the counts in them
  * only ever grow (one counter for the process), so whatever a workgroup still holds of such a record from an earlier chain is an OLDER count and at worst makes it look
  * again -- memory that had been pixels or levels before could read as a count from the future. */
-/* what the row's queue has written is out before the other queue's workgroup looks: on the device (xa_queue_follow), or -- X265AMD_QUEUE_FOLLOW=0 -- through the host
- * (the row's queue drained, a signalling command releases; the other queue acquires) */
-static hipError_t xa_follow_or_sync(void* follower, void* leader)
-{
-    static const bool follow = !(getenv("X265AMD_QUEUE_FOLLOW") && atoi(getenv("X265AMD_QUEUE_FOLLOW")) == 0);
-    if (follow) return xa_queue_follow(follower, leader);
-    if (xa_stream_sync(leader) != hipSuccess) return hipErrorUnknown;
-    return xa_stream_fence(follower, XA_CMD_ACQUIRE);
-}
+/* (what the row's queue has written is out before another queue's workgroup looks: on the device, xa_queue_follow) */
 static std::mutex g_chainLock;
 static std::vector<void*> g_chainFree;
 static const size_t kChainBlock = 4 * sizeof(x265amd_intra_peer) + sizeof(x265amd_intra_chain);
@@ -516,9 +508,8 @@ struct IntraRd
             if (rp->rdoq_level)
             {
                 /* RDOQ: the command makes its bit-estimate tables from nj.ctx (m_rqt[depth].cur: where every candidate and every chroma mode starts) */
-                static const bool nxn4Rdoq = !(getenv("X265AMD_NXN4_RDOQ") && atoi(getenv("X265AMD_NXN4_RDOQ")) == 0);
                 nj.rdoq_level = (uint8_t)rp->rdoq_level; nj.psy_rdoq_scale = rp->psy_rdoq_scale; nj.rdoq_tu_depth = (uint8_t)initTuDepth;
-                nj.rdoq_general = nxn4Rdoq ? 0 : 1;
+                nj.rdoq_general = 0;
                 x265amd_rdoq_lambda(qpLumaScaled, &nj.rdoq_lambda2[0], &nj.rdoq_lambda[0]);
                 x265amd_rdoq_lambda(qpChromaScaled, &nj.rdoq_lambda2[1], &nj.rdoq_lambda[1]);
                 nj.rdoq_lambda2[2] = nj.rdoq_lambda2[1]; nj.rdoq_lambda[2] = nj.rdoq_lambda[1];
@@ -532,9 +523,8 @@ struct IntraRd
     /* checkIntraInInter + encodeIntraInInter of this CU as one command (decided on the device) possible? */
     bool devIntraInInter() const
     {
-        static const bool on = !(getenv("X265AMD_DEVICE_IININTER") && atoi(getenv("X265AMD_DEVICE_IININTER")) == 0);
-        static const bool devRdoq = !(getenv("X265AMD_DEVICE_RDOQ") && atoi(getenv("X265AMD_DEVICE_RDOQ")) == 0);
-        return on && (!rp->rdoq_level || devRdoq) && !rp->fast_intra && log2 >= 3 && log2 <= 5 && range[0] == log2 && range[1] >= log2 && !si->tq_bypass_enabled;
+        static const bool devRdoq = xa_env_on("X265AMD_DEVICE_RDOQ");
+        return (!rp->rdoq_level || devRdoq) && !rp->fast_intra && log2 >= 3 && log2 <= 5 && range[0] == log2 && range[1] >= log2 && !si->tq_bypass_enabled;
     }
     void buildInInterJob(x265amd_intra_nxn_job& nj, uint64_t predTileM, uint64_t reconTileM, uint64_t cand, uint64_t coeffDev, void* levelsBuf, void* clevelsBuf)
     {
@@ -555,17 +545,13 @@ struct IntraRd
         x265amd_intra_nxn_out nxn;
         /* The device routine also takes the same CU coded 2Nx2N -- one 8x8 unit, num_units = 1, chroma decision included: one round trip instead of two and no
          * candidate bits on the host.  (It paid only once the bits of a unit were counted by a wavefront, a lane per context: a single lane needs 45 us for the 64
-         * coefficients.)  X265AMD_DEVICE_2Nx2N=0 takes the prediction-unit step with host bits instead. */
-        static const bool dev2Nx2N = !(getenv("X265AMD_DEVICE_2Nx2N") && atoi(getenv("X265AMD_DEVICE_2Nx2N")) == 0);
-        /* ... and the 16x16 CU coded 2Nx2N with its one 16x16 unit (chroma blocks 8x8): X265AMD_DEVICE_16=0 leaves it to the prediction-unit step */
-        static const bool dev16 = !(getenv("X265AMD_DEVICE_16") && atoi(getenv("X265AMD_DEVICE_16")) == 0);
-        static const bool dev32 = !(getenv("X265AMD_DEVICE_32") && atoi(getenv("X265AMD_DEVICE_32")) == 0);
+         * coefficients.)  Likewise the 16x16 and the 32x32 CU coded 2Nx2N with their one unit (chroma blocks 8x8 / 16x16). */
         /* RDOQ (round 5): the command makes the bit estimates itself and every chain runs Quant::rdoQuant (x265amd_intra_nxn_job.rdoq_level); X265AMD_DEVICE_RDOQ=0:
          * scan and chains as separate steps with the estimates from the host's contexts, as before */
-        static const bool devRdoq = !(getenv("X265AMD_DEVICE_RDOQ") && atoi(getenv("X265AMD_DEVICE_RDOQ")) == 0);
+        static const bool devRdoq = xa_env_on("X265AMD_DEVICE_RDOQ");
         const bool deviceNxN = (!rp->rdoq_level || devRdoq) && 2 + rdLevel + ((depth + initTuDepth) >> 1) <= MAX_JOBS &&
                                (partSize != 0 ? (log2 == 3 && log2TrSize == 2 && range[0] == 2)
-                                              : (dev2Nx2N && (log2 == 3 || (log2 == 4 && dev16) || (log2 == 5 && dev32)) && range[0] == log2 && range[1] >= log2));
+                                              : (log2 >= 3 && log2 <= 5 && range[0] == log2 && range[1] >= log2));
         const int devUnits = partSize != 0 ? 4 : 1, devLog2 = partSize != 0 ? 2 : 3, devN = 1 << devLog2;
         if (deviceNxN)
         {
@@ -607,7 +593,7 @@ struct IntraRd
                     buildDevJob(nj, 3, rdLevel, hintPred, hintRecon, (uint64_t)(uintptr_t)dCand2.p, (uint64_t)(uintptr_t)dCoeffDev2.p);
                     U(cuX, cuY).part_size = keep;
                     memcpy(dNxnJob2.p, &nj, sizeof(nj));
-                    if (xa_follow_or_sync(helper, st) != hipSuccess ||
+                    if (xa_queue_follow(helper, st) != hipSuccess ||
                         x265amd_intra_nxn(helper, (const x265amd_intra_nxn_job*)dNxnJob2.p, (x265amd_intra_nxn_out*)dNxnOut2.p) != X265AMD_OK)
                         return fail("intra rd: NxN step ahead");
                     ahead.on = true; ahead.x = cuX; ahead.y = cuY;
@@ -1093,12 +1079,11 @@ static int intra_cu_impl(int kind, int partSize, void* stream, const x265amd_sli
     if (kind == 3)
     {
         int started = 0;
-        /* on unless switched off (X265AMD_AHEAD_INTER=0).  Round 3 measured it 1-4 % slower (what the try hides, 40 us of device time per CU that gets to it, was eaten by
+        /* Round 3 measured it 1-4 % slower (what the try hides, 40 us of device time per CU that gets to it, was eaten by
          * what starting it costs every unskipped CU); since round 4 the CUs that end as skips never get here -- the device's skip chain ends them (inter_chain_dev.h) -- and
          * a CU that does is searched, predicted and coded while its intra try runs beside: 35.8 -> 40.9 frames/s on the bench clip */
-        static const bool aheadInter = !(getenv("X265AMD_AHEAD_INTER") && atoi(getenv("X265AMD_AHEAD_INTER")) == 0);
         IntraRd::Big& g = R.inter[R.log2 >= 3 && R.log2 <= 5 ? 5 - R.log2 : 0];
-        if (aheadInter && R.log2 >= 3 && R.log2 <= 5 && R.devIntraInInter() && xa_is_queue(R.st))
+        if (R.log2 >= 3 && R.log2 <= 5 && R.devIntraInInter() && xa_is_queue(R.st))
         {
             /* the queue of this depth: taken when the first CU of the CTU wants it (never waiting for one), given back with the CTU's working set */
             if (!g.q) { g.q = xa_queue_try_acquire(); g.owned = g.q != nullptr; }
@@ -1108,7 +1093,7 @@ static int intra_cu_impl(int kind, int partSize, void* stream, const x265amd_sli
                  g.levels.alloc(1024 * 2) != hipSuccess || g.clevels.alloc(2 * 256 * 2) != hipSuccess))
                 rc = xa_fail(X265AMD_EHIP, "intra rd: out of device memory");
         }
-        if (rc == X265AMD_OK && aheadInter && R.log2 >= 3 && R.log2 <= 5 && g.q && g.cand.p && R.devIntraInInter())
+        if (rc == X265AMD_OK && R.log2 >= 3 && R.log2 <= 5 && g.q && g.cand.p && R.devIntraInInter())
         {
             if (g.on) { g.on = false; if (xa_stream_sync(g.q) != hipSuccess) rc = xa_fail(X265AMD_EHIP, "intra rd: second queue"); }      /* an earlier try nobody collected */
             if (rc == X265AMD_OK)
@@ -1116,7 +1101,7 @@ static int intra_cu_impl(int kind, int partSize, void* stream, const x265amd_sli
                 x265amd_intra_nxn_job nj;
                 R.buildInInterJob(nj, d_pred, d_recon, (uint64_t)(uintptr_t)g.cand.p, (uint64_t)(uintptr_t)g.coeffDev.p, g.levels.p, g.clevels.p);
                 memcpy(g.job.p, &nj, sizeof(nj));
-                if (xa_follow_or_sync(g.q, R.st) != hipSuccess ||
+                if (xa_queue_follow(g.q, R.st) != hipSuccess ||
                     x265amd_intra_nxn(g.q, (const x265amd_intra_nxn_job*)g.job.p, (x265amd_intra_nxn_out*)g.out.p) != X265AMD_OK)
                     rc = xa_fail(X265AMD_EHIP, "intra rd: intra try ahead");
                 else { g.on = true; g.x = R.cuX; g.y = R.cuY; started = 1; }
@@ -1129,20 +1114,17 @@ static int intra_cu_impl(int kind, int partSize, void* stream, const x265amd_sli
     if (kind == 2)
     {
         /* only start the CU's 2Nx2N command (a 16x16 CU of an I picture, the third queue): the caller recurses into the sub-CUs and comes back with the ordinary call */
-        static const bool dev16 = !(getenv("X265AMD_DEVICE_16") && atoi(getenv("X265AMD_DEVICE_16")) == 0);
-        static const bool ahead16 = !(getenv("X265AMD_AHEAD_16") && atoi(getenv("X265AMD_AHEAD_16")) == 0);
-        static const bool dev32 = !(getenv("X265AMD_DEVICE_32") && atoi(getenv("X265AMD_DEVICE_32")) == 0);
         int started = 0;
         IntraRd::Big& g = R.big[R.log2 == 5 ? 1 : 0];
-        static const bool devRdoq = !(getenv("X265AMD_DEVICE_RDOQ") && atoi(getenv("X265AMD_DEVICE_RDOQ")) == 0);
-        if (ahead16 && ((R.log2 == 4 && dev16) || (R.log2 == 5 && dev32)) && g.q && g.cand.p && !g.on && (!rp->rdoq_level || devRdoq) && R.range[0] == R.log2 && R.range[1] >= R.log2 &&
+        static const bool devRdoq = xa_env_on("X265AMD_DEVICE_RDOQ");
+        if ((R.log2 == 4 || R.log2 == 5) && g.q && g.cand.p && !g.on && (!rp->rdoq_level || devRdoq) && R.range[0] == R.log2 && R.range[1] >= R.log2 &&
             2 + rp->rd_level + (R.depth >> 1) <= IntraRd::MAX_JOBS)
         {
             x265amd_intra_nxn_job nj;
             R.buildDevJob(nj, 0, rp->rd_level, d_pred, d_recon, (uint64_t)(uintptr_t)g.cand.p, (uint64_t)(uintptr_t)g.coeffDev.p, g.levels.p, g.clevels.p);
             nj.no_picture = 1;
             memcpy(g.job.p, &nj, sizeof(nj));
-            if (xa_follow_or_sync(g.q, R.st) != hipSuccess ||
+            if (xa_queue_follow(g.q, R.st) != hipSuccess ||
                 x265amd_intra_nxn(g.q, (const x265amd_intra_nxn_job*)g.job.p, (x265amd_intra_nxn_out*)g.out.p) != X265AMD_OK)
                 rc = xa_fail(X265AMD_EHIP, "intra rd: large unit step ahead");
             else { g.on = true; g.x = R.cuX; g.y = R.cuY; started = 1; }
@@ -1343,13 +1325,13 @@ int xa_intra_quad8_ws(void* stream, const x265amd_slice_info* si, const x265amd_
                       intptr_t stride, intptr_t cstride, int x, int y, int qp, const uint8_t* ctx, uint64_t frac, uint64_t split_recon, const uint64_t tilesN[2],
                       const uint64_t tiles2[2], x265amd_intra_cu8_result* results, void** ws, void (*between)(void*), void* between_ctx, int lambda_qp)
 {
-    static const bool on = !(getenv("X265AMD_INTRA_CHAIN") && atoi(getenv("X265AMD_INTRA_CHAIN")) == 0);
+    static const bool on = xa_env_on("X265AMD_INTRA_CHAIN");
     if (!on || !ws || !*ws || !xa_is_queue(stream)) return 1;
     IntraRd& R = *static_cast<IntraRd*>(*ws);
     void* helper = xa_queue_helper(stream);
     if (!helper || !R.dCand2.p || !R.dLayer.p || !R.dCand.p || R.ahead.on) return 1;
-    /* with RDOQ (round 5) the deciding command runs the general form of the evaluation and its own decision (intra_pu_dev.h); X265AMD_CHAIN_RDOQ=0: CU by CU */
-    static const bool chainRdoq = !(getenv("X265AMD_DEVICE_RDOQ") && atoi(getenv("X265AMD_DEVICE_RDOQ")) == 0) && !(getenv("X265AMD_CHAIN_RDOQ") && atoi(getenv("X265AMD_CHAIN_RDOQ")) == 0);
+    /* with RDOQ (round 5) the deciding command runs the general form of the evaluation and its own decision (intra_pu_dev.h); X265AMD_DEVICE_RDOQ=0: CU by CU */
+    static const bool chainRdoq = xa_env_on("X265AMD_DEVICE_RDOQ");
     /* delta QP (round 6): the CUs of the chain lie below the quantisation groups' depth, so no QP changes inside it -- but Search::checkIntra counts cu_qp_delta with
      * the coefficients of every CU that has any (codeCoeff with bCodeDQP, search.cpp:1266-1268): the deciding command adds those bins (nxn4_decide), the value is the
      * group's, known here */
@@ -1449,7 +1431,7 @@ int xa_intra_quad8_ws(void* stream, const x265amd_slice_info* si, const x265amd_
     R.c = nullptr;
     /* what this queue has written is out before the other workgroup looks (a signalling command releases), and that one looks (acquire) */
     int rc = X265AMD_OK;
-    if (xa_follow_or_sync(helper, stream) != hipSuccess) rc = xa_fail(X265AMD_EHIP, "intra rd: chain fence");
+    if (xa_queue_follow(helper, stream) != hipSuccess) rc = xa_fail(X265AMD_EHIP, "intra rd: chain fence");
     /* one command per role: the four records of a role run one after the other in the same workgroup */
     if (rc == X265AMD_OK && (x265amd_intra_nxn_list(helper, &jobs[1], 4, 2 * sizeof(x265amd_intra_nxn_job), &peers[0].out) != X265AMD_OK ||
                              x265amd_intra_nxn_list(stream, &jobs[0], 4, 2 * sizeof(x265amd_intra_nxn_job), (x265amd_intra_nxn_out*)R.dNxnOut.p) != X265AMD_OK))

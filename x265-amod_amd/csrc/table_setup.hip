@@ -247,9 +247,8 @@ hipError_t pool_alloc(int k, void** p, size_t bytes)
         /* Job records (host writes, device reads) live in DEVICE memory the host writes through the BAR: the stores are posted and travel in order ahead of
          * the command that uses them (or are long there when a kernel launches), and the device reads them at local latency instead of pulling them over
          * PCIe (about 1.7 us per command saved in queue mode).  Uncached allocation: nothing of it lingers in the L2 between uses.  Results (device
-         * writes, host reads) stay in pinned host memory: a host read over the BAR costs a microsecond per access.  X265AMD_PUSH_RECORDS=0: host memory for both. */
-        static const bool push = !(getenv("X265AMD_PUSH_RECORDS") && atoi(getenv("X265AMD_PUSH_RECORDS")) == 0);
-        device = k == POOL_MAPPED_IN && push;
+         * writes, host reads) stay in pinned host memory: a host read over the BAR costs a microsecond per access. */
+        device = k == POOL_MAPPED_IN;
         e = device ? hipExtMallocWithFlags(p, cls_bytes(c), hipDeviceMallocUncached) : hipHostMalloc(p, cls_bytes(c), hipHostMallocMapped | hipHostMallocCoherent);
     }
     if (e == hipSuccess)
@@ -345,12 +344,12 @@ void xa_copy_rects(void* st, const XaRects& r)
 #include <atomic>
 #include <string.h>
 #include <time.h>
-bool g_xaHostProf = getenv("X265AMD_HOSTPROF") != nullptr;
+bool g_xaHostProf = xa_env_present("X265AMD_HOSTPROF");
 namespace {
 struct HpEntry { const char* name; std::atomic<uint64_t> calls, ns; };
 HpEntry g_hp[128];
 std::atomic<int> g_hpN{ 0 };
-const bool g_hpWall = getenv("X265AMD_HOSTPROF") && !strcmp(getenv("X265AMD_HOSTPROF"), "wall");      /* X265AMD_HOSTPROF=wall: the scopes on the wall clock (parked time included) */
+const bool g_hpWall = xa_env_str("X265AMD_HOSTPROF") && !strcmp(xa_env_str("X265AMD_HOSTPROF"), "wall");      /* X265AMD_HOSTPROF=wall: the scopes on the wall clock (parked time included) */
 inline uint64_t hp_now()
 {
     if (!g_hpWall && xa_in_task()) return xa_task_run_ns_always();

@@ -7,6 +7,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include "../../include/x265amd.h"
+#include "xa_env.h"
 
 /* records the message for x265amd_last_error() and returns `code` */
 int xa_fail(int code, const char* msg);

@@ -43,10 +43,6 @@ void xa_fiber_set_thread_init(void (*fn)(void));
 /* general condition: an ordinary thread polls it; a task is parked and the condition is evaluated by whichever worker holds the task at that moment */
 void xa_wait_until(XaPred pred, void* ctx);
 int xa_in_task(void);
-/* inside a task: from now on its counter waits poll for up to `ns` nanoseconds before the task parks (0: park at once).  For the few tasks everything else waits
- * for -- the cut last CTU row of a picture that others reference: hundreds of device answers per CTU, each a few microseconds away, and a parked task comes back only
- * when a worker is free to look */
-void xa_task_spin_ns(uint64_t ns);
 int xa_worker_count(void);
 /* X265AMD_TIMING: the calling task's waits are booked under a class (0..3; returns the class in force before); xa_task_parked_ns: the totals so far */
 int xa_task_wait_class(int cls);

@@ -245,7 +245,7 @@ static int sao_rdo_range(const x265amd_slice_info* si, int referenced, int frame
                          int ctu_row_begin, int ctu_row_end, int colBegin, int colEnd, uint8_t* carry)
 {
     if (!si || !units || !count || !offset_org || !depth_sao_rate || !params || !sao_flags) return X265AMD_EINVAL;
-    const int ctuW = (si->pic_width + 63) >> 6, ctuH = (si->pic_height + 63) >> 6, numCtu = ctuW * ctuH, w4 = si->pic_width >> 2;
+    const int ctuW = (si->pic_width + 63) >> 6, ctuH = (si->pic_height + 63) >> 6, w4 = si->pic_width >> 2;
     if (ctu_row_begin < 0 || ctu_row_begin >= ctu_row_end || ctu_row_end > ctuH) return X265AMD_EINVAL;
     const bool whole = ctu_row_begin == 0 && ctu_row_end == ctuH;
     if (!whole && frame_threads == 1) return X265AMD_EINVAL;
@@ -257,7 +257,6 @@ static int sao_rdo_range(const x265amd_slice_info* si, int referenced, int frame
         if (refDepth > 0 && depth_sao_rate[refDepth - 1] > 0.75) sao_flags[0] = 0;
         if (refDepth > 0 && depth_sao_rate[4 + refDepth - 1] > 0.5) sao_flags[1] = 0;
     }
-    int numNoSao[2] = { 0, 0 };
     static const uint8_t chromaScale[70] = { 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23, 24, 25, 26, 27, 28, 29, 29, 30, 31, 32, 33, 33, 34, 34,
                                              35, 35, 36, 36, 37, 37, 38, 39, 40, 41, 42, 43, 44, 45, 46, 47, 48, 49, 50, 51, 51, 51, 51, 51, 51, 51, 51, 51, 51, 51, 51, 51 };
     Rdo* R = new Rdo;
@@ -327,8 +326,6 @@ static int sao_rdo_range(const x265amd_slice_info* si, int referenced, int frame
                 if (sao_flags[1]) { p.type[1] = src.type[1]; for (int pl = 1; pl < 3; pl++) { p.band_pos[pl] = src.band_pos[pl]; memcpy(p.offset[pl], src.offset[pl], 4); } }
             }
         }
-        if (p.type[0] < 0) numNoSao[0]++;
-        if (p.type[1] < 0) numNoSao[1]++;
         R->load(R->temp);
         R->store(R->cur);
     }
@@ -337,13 +334,7 @@ static int sao_rdo_range(const x265amd_slice_info* si, int referenced, int frame
      * reconstruction flag is set before it has set the last row's own (framefilter.cpp:622-647 against :650-664; without wavefronts the rows are filtered one after the
      * other by the same function, frameencoder.cpp:928-960), so the rates stay at their initial zero and SAO is never switched off by the picture before (seen in the
      * reference's own objects: all eight rates 0.000 after every picture of a --frame-threads 1 encode; the fixtures rc_ft1/ and cli_nowpp_ft1/ pin it -- rounds 2 to 6
-     * had the update for pictures without wavefronts, which only a --no-wpp --frame-threads 1 encode ever showed).  X265AMD_SAO_RATES=1: the update as SAO::rdoSaoUnitRowEnd has it. */
-    static const bool rates = getenv("X265AMD_SAO_RATES") && atoi(getenv("X265AMD_SAO_RATES")) != 0;
-    if (whole && rates)
-    {
-        depth_sao_rate[refDepth] = sao_flags[0] ? numNoSao[0] / (double)numCtu : 1.0;
-        depth_sao_rate[4 + refDepth] = sao_flags[1] ? numNoSao[1] / (double)numCtu : 1.0;
-    }
+     * had the update for pictures without wavefronts, which only a --no-wpp --frame-threads 1 encode ever showed). */
     x265amd_cabac_close(R->c);
     delete R;
     return X265AMD_OK;

@@ -1,6 +1,7 @@
 /* Row tasks on a fixed set of host threads: see csrc/xa_fiber.h.  Host C++ (no reference counterpart: the reference runs its CTU rows as jobs of its own
  * thread pool, source/common/threadpool.cpp / wavefront.cpp, with the pixel work done by the thread itself, so a row never waits for a device). */
 #include "../csrc/xa_fiber.h"
+#include "../csrc/xa_env.h"
 #include <atomic>
 #include <condition_variable>
 #include <mutex>
@@ -51,14 +52,13 @@ struct Fiber
     uint64_t stintStart = 0;            /* when it was last resumed */
     uint64_t userMark = 0;              /* for the caller's phase accounting */
     void* userSlot = nullptr;           /* a pointer of the caller's (the row's reference-picture guard) */
-    uint64_t spinNs = 0;                /* xa_task_spin_ns: how long a wait polls before the task parks */
     int waitClass = 0; uint64_t parkedNs[4] = { 0, 0, 0, 0 };      /* X265AMD_TIMING: time spent in waits by the class the caller named (xa_task_wait_class) */
     struct Worker* worker = nullptr;    /* the worker running it now */
 };
 
 struct Worker { void* sp = nullptr; Fiber* cur = nullptr; };
 std::atomic<uint64_t> g_busyNs{ 0 }, g_idleNs{ 0 }, g_switches{ 0 };
-const bool g_stats = getenv("X265AMD_TIMING") != nullptr || getenv("X265AMD_HOSTPROF") != nullptr;
+const bool g_stats = xa_env_present("X265AMD_TIMING") || xa_env_present("X265AMD_HOSTPROF");
 inline uint64_t now_ns() { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (uint64_t)ts.tv_sec * 1000000000ull + (uint64_t)ts.tv_nsec; }
 
 struct Sched
@@ -80,7 +80,7 @@ __attribute__((noinline)) Worker* current_worker() { return t_worker; }
 
 int default_workers()
 {
-    if (const char* e = getenv("X265AMD_WORKERS")) { const int n = atoi(e); if (n > 0) return n > 256 ? 256 : n; }
+    if (const char* e = xa_env_str("X265AMD_WORKERS")) { const int n = atoi(e); if (n > 0) return n > 256 ? 256 : n; }
     int n = (int)std::thread::hardware_concurrency();
     if (n <= 0) n = 8;
     /* cgroup v2 CPU quota: "<quota> <period>" or "max <period>" */
@@ -282,7 +282,6 @@ uint64_t xa_task_run_ns_always(void) { Worker* w = current_worker(); return w &&
 uint64_t* xa_task_mark(void) { Worker* w = current_worker(); return w && w->cur ? &w->cur->userMark : nullptr; }
 void xa_sched_stats(uint64_t out[3]) { out[0] = g_busyNs.load(); out[1] = g_idleNs.load(); out[2] = g_switches.load(); }
 int xa_in_task(void) { Worker* w = current_worker(); return w && w->cur; }
-void xa_task_spin_ns(uint64_t ns) { Worker* w = current_worker(); if (w && w->cur) w->cur->spinNs = ns; }
 int xa_task_wait_class(int cls) { Worker* w = current_worker(); if (!(w && w->cur)) return 0; const int old = w->cur->waitClass; w->cur->waitClass = cls & 3; return old; }
 void xa_task_parked_ns(uint64_t out[4]) { Worker* w = current_worker(); for (int k = 0; k < 4; k++) out[k] = w && w->cur ? w->cur->parkedNs[k] : 0; }
 
@@ -310,7 +309,7 @@ void xa_tasks_run(const XaTask* tasks, int n)
                 int expect = ST_EMPTY;
                 if (f.state.load(std::memory_order_acquire) != ST_EMPTY || !f.state.compare_exchange_strong(expect, ST_RUNNING, std::memory_order_acq_rel)) continue;
                 f.task = tasks[k]; f.group = &grp; f.pred = nullptr; f.predCtx = nullptr; f.sp = nullptr; f.stack = nullptr; f.scratchList = nullptr; f.worker = nullptr;
-                f.waitCounter.store(nullptr); f.waitValue.store(0); f.deadlineNs.store(0); f.runNs = 0; f.userMark = 0; f.userSlot = nullptr; f.spinNs = 0;
+                f.waitCounter.store(nullptr); f.waitValue.store(0); f.deadlineNs.store(0); f.runNs = 0; f.userMark = 0; f.userSlot = nullptr;
                 int hw = S.highWater.load(std::memory_order_acquire);
                 while (hw < i + 1 && !S.highWater.compare_exchange_weak(hw, i + 1, std::memory_order_acq_rel)) {}
                 S.live.fetch_add(1, std::memory_order_acq_rel);
@@ -337,7 +336,6 @@ void xa_wait_counter(const volatile uint64_t* counter, uint64_t value)
         Fiber* f = w->cur;
         f->pred = nullptr;
         const uint64_t tw0 = g_stats ? now_ns() : 0;
-        if (f->spinNs) { const uint64_t t1 = now_ns() + f->spinNs; while (*counter < value && now_ns() < t1) _mm_pause(); if (*counter >= value) { if (g_stats) f->parkedNs[f->waitClass] += now_ns() - tw0; return; } }
         do
         {
             f->waitValue.store(value, std::memory_order_release); f->waitCounter.store(counter, std::memory_order_release);
@@ -366,7 +364,6 @@ int xa_wait_counter_deadline(const volatile uint64_t* counter, uint64_t value, u
         f->pred = nullptr;
         int rc = 0;
         const uint64_t tw0 = g_stats ? now_ns() : 0;
-        if (f->spinNs) { const uint64_t t1 = now_ns() + f->spinNs; while (*counter < value && now_ns() < t1) _mm_pause(); if (*counter >= value) { if (g_stats) f->parkedNs[f->waitClass] += now_ns() - tw0; return 0; } }
         do
         {
             f->deadlineNs.store(deadline, std::memory_order_release);

@@ -91,6 +91,80 @@ class call_stream:
         return False
 
 
+class held_queue:
+    """a device job queue held for a `with` block, whatever X265AMD_TEST_QUEUE says: yields the handle (the `stream` argument of the entry points), gives the
+    queue back on exit.  No queue because the environment carries X265AMD_QUEUES=0: the test is skipped with that reason; no queue otherwise: a failure.
+
+    While a queue is held the resident job server is running, and a device-wide wait behind it hangs ("Round 6, at the very end": a
+    hipDeviceSynchronize behind the resident job server).  So:
+      * every upload, every torch.zeros and ONE torch.cuda.synchronize() happen BEFORE the block is entered;
+      * inside the block there are only calls into the library;
+      * x265amd_queue_release fences and drains the queue (xa_queue_release: a releasing fence, then xa_stream_sync), so for the entry points that only enqueue
+        (tu_chain, intra_tu_chain, intra_scan, motion_compensation, inter_cost, me_search) the release IS the wait: results are read back only AFTER the block;
+      * one queue per case, and no device buffer is used by two cases under one held queue: the server looks at memory afresh only for the commands that ask
+        for it (k_job_server: XA_CMD_ACQUIRE and the copy / table-reading commands).
+    The runners below take `stream=None` or a held_queue that has NOT been entered yet: they upload, synchronise once, enter it around their library call
+    and leave it before they read anything back (stream_scope)."""
+
+    def __init__(self, L):
+        self.lib = L.lib if hasattr(L, "lib") else L
+        self.h = None
+
+    def __enter__(self):
+        self.lib.x265amd_queue_acquire.restype = C.c_void_p
+        self.h = self.lib.x265amd_queue_acquire()
+        if not self.h:
+            if os.environ.get("X265AMD_QUEUES") == "0":
+                import pytest
+                pytest.skip("X265AMD_QUEUES=0: no device job queues")
+            raise AssertionError("x265amd_queue_acquire returned NULL although X265AMD_QUEUES is not 0")
+        return C.c_void_p(self.h)
+
+    def __exit__(self, *exc):
+        if self.h:
+            self.lib.x265amd_queue_release(C.c_void_p(self.h))
+            self.h = None
+        return False
+
+
+class stream_scope:
+    """the `stream` parameter of a runner: None -> the NULL stream; a held_queue (not entered) -> everything the runner has uploaded so far is waited for, then
+    the queue is held for the block.  After the block the results may be read (NULL stream: after a torch.cuda.synchronize(), which this does on exit)."""
+
+    def __init__(self, stream):
+        assert stream is None or isinstance(stream, held_queue), "stream: None or a held_queue that has not been entered"
+        self.q = stream
+
+    def __enter__(self):
+        import torch
+        torch.cuda.synchronize()
+        return self.q.__enter__() if self.q is not None else None
+
+    def __exit__(self, *exc):
+        if self.q is not None:
+            self.q.__exit__(*exc)
+        if exc[0] is None:
+            import torch
+            torch.cuda.synchronize()
+        return False
+
+
+# enum XaOp (csrc/xa_queue.h:17-21), in its order: x265amd_queue_stats reports command kind k at out[10 + 3 * k]
+XA_OPS = ("NOP", "EXIT", "COPY", "COPY2D", "FILL", "COPY_RECTS", "MC", "MC_COST", "CU_MEASURE", "TU_CHAIN", "TU_CHAIN_RDOQ", "INTRA_TU_CHAIN", "INTRA_TU_CHAIN_RDOQ",
+          "INTRA_SCAN", "ME_SEARCH", "ME_SEARCH_STAR", "ME_DEFERRED", "EST_BIT", "INTRA_PU", "INTRA_NXN", "INTER_CHAIN", "INTER_SEARCH", "WAIT")
+XA_OP = {name: k for k, name in enumerate(XA_OPS)}
+XA_SERVER_WAVES = 8
+
+
+def queue_stats(L, reset=0, algorithmic_bytes=False):
+    """x265amd_queue_stats (valid only while no queue is held): {command kind: commands the job server ran since the last reset}; algorithmic_bytes=True: the bytes
+    its jobs had to read and write instead (every job body adds its own figure once, so a job run twice shows there and nowhere else)"""
+    out = np.zeros(106, np.uint64)
+    lib = L.lib if hasattr(L, "lib") else L
+    assert lib.x265amd_queue_stats(_ptr(out), 106, reset) == 0
+    return {name: int(out[(12 if algorithmic_bytes else 10) + 3 * k]) for k, name in enumerate(XA_OPS)}
+
+
 def oracle_path(depth):
     return os.path.join(ORACLE_DIR, "liboracle%d.so" % depth)
 
@@ -713,10 +787,16 @@ class HipME:
         d_reftab = self.upload(refs)
         if flags is None:
             flags = (1 if ((packed_ordered["method"] & 0x7f) == ME_STAR).any() else 0) | (2 if (packed_ordered["method"] & 0x80).any() else 0)
-        rc = self.lib.x265amd_me_search(self.ctx, C.c_void_p(stream or 0), C.c_void_p(d_cur.data_ptr() + origin_elems * itemsize),
-                                        C.c_void_p(d_reftab.data_ptr()), C.c_int64(stride), C.c_void_p(d_groups.data_ptr()), len(groups),
-                                        C.c_void_p(d_jobs.data_ptr()), C.c_void_p(d_out.data_ptr()), max_win[0], max_win[1], flags,
-                                        C.c_void_p(d_chroma.data_ptr() if d_chroma is not None else 0), C.c_int64(cstride))
+        def call(st):
+            return self.lib.x265amd_me_search(self.ctx, st, C.c_void_p(d_cur.data_ptr() + origin_elems * itemsize),
+                                              C.c_void_p(d_reftab.data_ptr()), C.c_int64(stride), C.c_void_p(d_groups.data_ptr()), len(groups),
+                                              C.c_void_p(d_jobs.data_ptr()), C.c_void_p(d_out.data_ptr()), max_win[0], max_win[1], flags,
+                                              C.c_void_p(d_chroma.data_ptr() if d_chroma is not None else 0), C.c_int64(cstride))
+        if isinstance(stream, held_queue):      # not entered yet: held around the call alone, after the uploads above (see held_queue)
+            with stream_scope(stream) as st:
+                rc = call(st)
+        else:
+            rc = call(C.c_void_p(stream or 0))
         assert rc == 0, self.lib.x265amd_last_error()
         self._keep = (d_groups, d_jobs, d_reftab)
         return d_out
@@ -822,6 +902,59 @@ TU_RESULT_DT = np.dtype([("num_sig", "<u4"), ("zero_energy", "<u4"), ("nz_energy
 assert TU_JOB_DT.itemsize == 64 and TU_RESULT_DT.itemsize == 32
 
 
+def tu_chain_run_hip(L, cases, depth, stream=None):
+    """x265amd_tu_chain on a batch in one arena (per case fenc | pred | recon | coeff | resi at stride 32); same return shape as tu_run_chain_oracle:
+    list of (stats[5], coeff, resi, recon)"""
+    import torch
+    dt = np.uint8 if depth == 8 else np.uint16
+    isz = np.dtype(dt).itemsize
+    per = 32 * 32 * (isz * 3 + 2 * 2)
+    arena = np.zeros(len(cases) * per, np.uint8)
+    jobs = np.zeros(len(cases), TU_JOB_DT)
+    for i, c in enumerate(cases):
+        N = 1 << c["log2"]
+        base = i * per
+        f = arena[base:base + 1024 * isz].view(dt).reshape(32, 32); f[:N, :N] = c["fenc"]
+        p = arena[base + 1024 * isz:base + 2048 * isz].view(dt).reshape(32, 32); p[:N, :N] = c["pred"]
+        jobs[i] = (0, 0, 0, 0, 0, 32, 32, 32, 32, c["log2"], c["ttype"], c["intra"], c["dir"], c["slice"], c["qp"], c["signhide"], 0)
+    d_arena = torch.from_numpy(arena).cuda()
+    a0 = d_arena.data_ptr()
+    for i in range(len(cases)):
+        base = a0 + i * per
+        jobs[i]["fenc"] = base; jobs[i]["pred"] = base + 1024 * isz
+        jobs[i]["recon"] = base + 2048 * isz; jobs[i]["coeff"] = base + 3072 * isz; jobs[i]["resi"] = base + 3072 * isz + 2048
+    d_jobs = torch.from_numpy(jobs.view(np.uint8).copy()).cuda()
+    d_out = torch.zeros(len(cases) * TU_RESULT_DT.itemsize, dtype=torch.uint8, device="cuda")
+    with stream_scope(stream) as st:
+        rc = L.lib.x265amd_tu_chain(st, C.c_void_p(d_jobs.data_ptr()), len(cases), C.c_void_p(d_out.data_ptr()))
+    assert rc == 0
+    return tu_chain_unpack(cases, d_out.cpu().numpy().view(TU_RESULT_DT), d_arena.cpu().numpy(), per, dt)
+
+
+def tu_chain_unpack(cases, res, back, per, dt):
+    isz = np.dtype(dt).itemsize
+    out = []
+    for i, c in enumerate(cases):
+        N = 1 << c["log2"]
+        base = i * per
+        st = np.array([res[i]["num_sig"], res[i]["zero_dist"], res[i]["zero_energy"], res[i]["nz_dist"], res[i]["nz_energy"]], np.uint64)
+        out.append((st, back[base + 3072 * isz:base + 3072 * isz + N * N * 2].view(np.int16).copy(),
+                    back[base + 3072 * isz + 2048:base + 3072 * isz + 4096].view(np.int16).reshape(32, 32)[:N, :N].copy(),
+                    back[base + 2048 * isz:base + 3072 * isz].view(dt).reshape(32, 32)[:N, :N].copy()))
+    return out
+
+
+def tu_chain_assert(got, want, cases, what):
+    """(stats, coeff, resi, recon) per unit, product against oracle; the message names the operation, the unit and its size"""
+    assert len(got) == len(want) == len(cases)
+    for i, (c, g, w) in enumerate(zip(cases, got, want)):
+        tag = "%s: unit %d of %d (%dx%d)" % (what, i, len(cases), 1 << c["log2"], 1 << c["log2"])
+        assert tuple(int(v) for v in g[0]) == tuple(int(v) for v in w[0]), "%s: (numSig, dist0, energy0, dist, energy) %s, want %s" % (tag, g[0], w[0])
+        assert np.array_equal(g[3], w[3]), tag + ": reconstruction"
+        assert np.array_equal(g[1], w[1]), tag + ": levels"
+        assert np.array_equal(g[2], w[2]), tag + ": residual"
+
+
 # ----------------------------------------------------------------------------------------------------------
 # intra cases: neighbour set (initAdiPattern) + 35-mode sa8d scan
 # ----------------------------------------------------------------------------------------------------------
@@ -887,7 +1020,7 @@ INTRA_JOB_DT = np.dtype([("recon", "<u8"), ("fenc", "<u8"), ("avail", "<u8"), ("
 assert INTRA_JOB_DT.itemsize == 40
 
 
-def intra_run_hip(L, cases):
+def intra_run_hip(L, cases, stream=None):
     """x265amd_intra_scan on a batch; same return shape as intra_run_host"""
     import torch
     isz = cases[0]["plane"].itemsize
@@ -906,9 +1039,9 @@ def intra_run_hip(L, cases):
     d_jobs = torch.from_numpy(jobs.view(np.uint8).copy()).cuda()
     d_sa = torch.zeros(len(cases) * 35, dtype=torch.int32, device="cuda")
     d_nb = torch.zeros(len(cases) * 2 * 129 * isz, dtype=torch.uint8, device="cuda")
-    rc = L.lib.x265amd_intra_scan(None, C.c_void_p(d_jobs.data_ptr()), len(cases), C.c_void_p(d_sa.data_ptr()), C.c_void_p(d_nb.data_ptr()))
+    with stream_scope(stream) as st:
+        rc = L.lib.x265amd_intra_scan(st, C.c_void_p(d_jobs.data_ptr()), len(cases), C.c_void_p(d_sa.data_ptr()), C.c_void_p(d_nb.data_ptr()))
     assert rc == 0
-    torch.cuda.synchronize()
     sa = d_sa.cpu().numpy().reshape(-1, 35)
     nb = d_nb.cpu().numpy().view(cases[0]["plane"].dtype).reshape(-1, 2, 129)
     out = []
@@ -1013,7 +1146,7 @@ def mc_digest(res):
     return h.digest()
 
 
-def mc_run_hip(L, pics, stride, cstride, org, jobs):
+def mc_run_hip(L, pics, stride, cstride, org, jobs, stream=None):
     """x265amd_motion_compensation on device memory; same return shape as mc_run_host"""
     import torch
     n = len(jobs)
@@ -1031,10 +1164,10 @@ def mc_run_hip(L, pics, stride, cstride, org, jobs):
     jb["dstV"] = d_v.data_ptr() + np.arange(n) * 32 * 32 * isz
     jb["dstStride"], jb["dstCStride"] = 64, 32
     d_jobs = torch.from_numpy(jb.view(np.uint8).copy()).cuda()
-    rc = L.lib.x265amd_motion_compensation(None, C.c_void_p(d_planes.data_ptr()), C.c_int64(stride), C.c_int64(cstride), MC_W, MC_H,
-                                           C.c_void_p(d_jobs.data_ptr()), n)
+    with stream_scope(stream) as st:
+        rc = L.lib.x265amd_motion_compensation(st, C.c_void_p(d_planes.data_ptr()), C.c_int64(stride), C.c_int64(cstride), MC_W, MC_H,
+                                               C.c_void_p(d_jobs.data_ptr()), n)
     assert rc == 0
-    torch.cuda.synchronize()
     outY = d_y.cpu().numpy().view(dt).reshape(n, 64, 64); outU = d_u.cpu().numpy().view(dt).reshape(n, 32, 32); outV = d_v.cpu().numpy().view(dt).reshape(n, 32, 32)
     res = []
     for i in range(n):
@@ -1164,6 +1297,71 @@ def rdoq_chain_oracle(L, cases):
     return out
 
 
+def est_bit_run_hip(L, ctxs, shapes, stream=None):
+    """x265amd_est_bit on a batch: ctxs [n, 160] context states, shapes[i] = (log2, is_luma); returns int32 [n, EST_INTS]"""
+    import torch
+    n = len(ctxs)
+    jobs = np.zeros(n, EST_JOB_DT)
+    d_ctx = torch.from_numpy(np.ascontiguousarray(ctxs)).cuda()
+    d_est = torch.zeros(n * EST_INTS, dtype=torch.int32, device="cuda")
+    for i, (l, lu) in enumerate(shapes):
+        jobs[i] = (d_ctx.data_ptr() + i * 160, d_est.data_ptr() + i * EST_INTS * 4, l, lu, 0)
+    d_jobs = torch.from_numpy(jobs.view(np.uint8).copy()).cuda()
+    with stream_scope(stream) as st:
+        rc = L.lib.x265amd_est_bit(st, C.c_void_p(d_jobs.data_ptr()), n)
+    assert rc == 0
+    return d_est.cpu().numpy().reshape(n, EST_INTS)
+
+
+def tu_chain_rdoq_run_hip(L, cases, stream=None, coeff_bits=False):
+    """x265amd_tu_chain_rdoq on a batch (jobs with rdoq == 0 quantise plainly), estBit tables from the oracle; list of (stats[5], coeff, resi, recon) as
+    rdoq_chain_oracle.  coeff_bits=True (NULL stream only): x265amd_coeff_bits on the levels just written, and (chain results, bits [n], contexts out [n, 160])"""
+    import torch
+    assert not (coeff_bits and stream is not None)
+    orc = load_oracle(L.depth)
+    dt = L.pixel
+    isz = np.dtype(dt).itemsize
+    n = len(cases)
+    per = 32 * 32 * (isz * 3 + 2 * 2)
+    arena = np.zeros(n * per, np.uint8)
+    ests = np.stack([est_bit(orc, c["ctx"], c["log2"], int(c["ttype"] == 0)) for c in cases])
+    ctxs = np.zeros((n, 160), np.uint8)
+    for i, c in enumerate(cases):
+        N = 1 << c["log2"]
+        base = i * per
+        arena[base:base + 1024 * isz].view(dt).reshape(32, 32)[:N, :N] = c["fenc"]
+        arena[base + 1024 * isz:base + 2048 * isz].view(dt).reshape(32, 32)[:N, :N] = c["pred"]
+        ctxs[i, :CTX_COUNT] = c["ctx"]
+    d_arena = torch.from_numpy(arena).cuda()
+    d_est = torch.from_numpy(ests).cuda()
+    d_ctx = torch.from_numpy(ctxs).cuda()
+    d_ctx_out = torch.zeros_like(d_ctx)
+    a0 = d_arena.data_ptr()
+    jobs = np.zeros(n, TU_JOB_DT); rq = np.zeros(n, TU_RDOQ_DT); cb = np.zeros(n, COEFF_BITS_JOB_DT)
+    for i, c in enumerate(cases):
+        base = a0 + i * per
+        jobs[i] = (base, base + 1024 * isz, base + 3072 * isz, base + 3072 * isz + 2048, base + 2048 * isz, 32, 32, 32, 32,
+                   c["log2"], c["ttype"], c["intra"], c["dir"], c["slice"], c["qp"], c["signhide"], 0)
+        l2, l1 = C.c_int64(0), C.c_int32(0)
+        L.lib.x265amd_rdoq_lambda(c["qp"], C.byref(l2), C.byref(l1))
+        rq[i] = (d_est.data_ptr() + i * EST_INTS * 4, l2.value, l1.value, c["psyrdoq"], c["rdoq"], c["tudepth"], 0)
+        cb[i] = (base + 3072 * isz, d_ctx.data_ptr() + i * 160, d_ctx_out.data_ptr() + i * 160, c["log2"], c["ttype"], c["intra"], c["dir"], c["signhide"], 0)
+    d_jobs = torch.from_numpy(jobs.view(np.uint8).copy()).cuda()
+    d_rq = torch.from_numpy(rq.view(np.uint8).copy()).cuda()
+    d_cb = torch.from_numpy(cb.view(np.uint8).copy()).cuda()
+    d_out = torch.zeros(n * TU_RESULT_DT.itemsize, dtype=torch.uint8, device="cuda")
+    d_bits = torch.zeros(n, dtype=torch.int64, device="cuda")
+    with stream_scope(stream) as st:
+        rc = L.lib.x265amd_tu_chain_rdoq(st, C.c_void_p(d_jobs.data_ptr()), C.c_void_p(d_rq.data_ptr()), n, C.c_void_p(d_out.data_ptr()))
+        assert rc == 0
+        if coeff_bits:
+            assert L.lib.x265amd_coeff_bits(None, C.c_void_p(d_cb.data_ptr()), n, C.c_void_p(d_bits.data_ptr())) == 0
+    chain = tu_chain_unpack(cases, d_out.cpu().numpy().view(TU_RESULT_DT), d_arena.cpu().numpy(), per, dt)
+    if coeff_bits:
+        return chain, d_bits.cpu().numpy().astype(np.uint64), d_ctx_out.cpu().numpy()
+    return chain
+
+
 # ---- distortion of inter prediction candidates (x265amd_inter_cost): MC jobs + a metric ----
 def inter_cost_jobs(seed, n):
     """mc_jobs with the decision metrics of the reference: SAD (selectMVP), SATD (+chroma: mergeEstimation / bi-prediction
@@ -1220,7 +1418,7 @@ def inter_cost_run_host(L, pics, fenc, stride, cstride, org, jobs):
     return cost, [outY[i, :int(jobs[i]["h"]), :int(jobs[i]["w"])].copy() for i in range(n)]
 
 
-def inter_cost_run_hip(L, pics, fenc, stride, cstride, org, jobs):
+def inter_cost_run_hip(L, pics, fenc, stride, cstride, org, jobs, stream=None):
     import torch
     n = len(jobs)
     dt = pics[0].dtype
@@ -1241,11 +1439,11 @@ def inter_cost_run_hip(L, pics, fenc, stride, cstride, org, jobs):
     jb["dstStride"], jb["dstCStride"] = 64, 32
     d_jobs = torch.from_numpy(jb.view(np.uint8).copy()).cuda()
     d_cost = torch.zeros(n * 2, dtype=torch.int32, device="cuda")
-    rc = L.lib.x265amd_inter_cost(None, C.c_void_p(d_planes.data_ptr()), C.c_int64(stride), C.c_int64(cstride), MC_W, MC_H,
-                                  C.c_void_p(d_jobs.data_ptr()), n, C.c_void_p(d_fplanes.data_ptr()), C.c_int64(stride), C.c_int64(cstride),
-                                  C.c_void_p(d_cost.data_ptr()))
+    with stream_scope(stream) as st:
+        rc = L.lib.x265amd_inter_cost(st, C.c_void_p(d_planes.data_ptr()), C.c_int64(stride), C.c_int64(cstride), MC_W, MC_H,
+                                      C.c_void_p(d_jobs.data_ptr()), n, C.c_void_p(d_fplanes.data_ptr()), C.c_int64(stride), C.c_int64(cstride),
+                                      C.c_void_p(d_cost.data_ptr()))
     assert rc == 0
-    torch.cuda.synchronize()
     outY = d_y.cpu().numpy().view(dt).reshape(n, 64, 64)
     return d_cost.cpu().numpy().view(np.uint32).reshape(n, 2), [outY[i, :int(jobs[i]["h"]), :int(jobs[i]["w"])].copy() for i in range(n)]
 
@@ -1340,7 +1538,7 @@ def intra_tu_unpack(cases, res, arena, per):
     return out
 
 
-def intra_tu_run_hip(L, cases):
+def intra_tu_run_hip(L, cases, stream=None):
     import torch
     n = len(cases)
     dt = cases[0]["plane"].dtype
@@ -1358,10 +1556,10 @@ def intra_tu_run_hip(L, cases):
     d_jobs = torch.from_numpy(jobs.view(np.uint8).copy()).cuda()
     d_rq = torch.from_numpy(rq.view(np.uint8).copy()).cuda()
     d_out = torch.zeros(n * TU_RESULT_DT.itemsize, dtype=torch.uint8, device="cuda")
-    rc = L.lib.x265amd_intra_tu_chain(None, C.c_void_p(d_jobs.data_ptr()), C.c_void_p(d_rq.data_ptr()) if any(c["rdoq"] for c in cases) else None, n,
-                                      C.c_void_p(d_out.data_ptr()))
+    with stream_scope(stream) as st:
+        rc = L.lib.x265amd_intra_tu_chain(st, C.c_void_p(d_jobs.data_ptr()), C.c_void_p(d_rq.data_ptr()) if any(c["rdoq"] for c in cases) else None, n,
+                                          C.c_void_p(d_out.data_ptr()))
     assert rc == 0
-    torch.cuda.synchronize()
     return intra_tu_unpack(cases, d_out.cpu().numpy().view(TU_RESULT_DT), d_arena.cpu().numpy(), per)
 
 
@@ -2159,6 +2357,120 @@ RD_SCRATCH_ELEMS = 4 * 4096 + 6 * 1024
 RD_SEL_BYTES = 384
 
 
+def cu_measure_expected(O, depth, src_planes, stride, cstride, cus, tiles):
+    """the whole x265amd_cu_measure record per CU from the primitives of `O` (oracle, or the reference build) and numpy: src_planes = [Y, U, V] flat source
+    planes with strides in samples, cus = RD_CU_DT records (x, y, log2_size), tiles[i] = CU i's RD_TILE (Y stride 64 | U | V stride 32).
+      sse[p] = sse_pp; psy = psyCost_pp on luma; sa8d_luma = cu[log2 - 2].sa8d; sa8d = luma + cu[log2 - 3].sa8d of U and V (the 4x4 chroma of an 8x8 CU:
+      cu[0].sa8d = satd_4x4, pixel.cpp:1171); src_mean = sum // S^2; src_homo = sum |v - mean| // S^2 (Analysis::complexityCheckCU, analysis.cpp:3538-3559)"""
+    dt = np.uint8 if depth == 8 else np.uint16
+    out = np.zeros(len(cus), CU_MEASURE_DT)
+    for i, cu in enumerate(cus):
+        log2 = int(cu["log2_size"]); S = 1 << log2
+        for p in range(3):
+            s, ts, st = (S, 64, stride) if p == 0 else (S // 2, 32, cstride)
+            o = 0 if p == 0 else 4096 + (p - 1) * 1024
+            x, y = (int(cu["x"]), int(cu["y"])) if p == 0 else (int(cu["x"]) // 2, int(cu["y"]) // 2)
+            plane = np.asarray(src_planes[p]).reshape(-1, st)
+            fenc = np.ascontiguousarray(plane[y:y + s, x:x + s].astype(dt))
+            blk = np.ascontiguousarray(np.asarray(tiles[i])[o:o + ts * ts].reshape(ts, ts)[:s, :s].astype(dt))
+            idx = log2 - 2 if p == 0 else log2 - 3
+            out[i]["sse"][p] = O.call("sse_pp", idx, fenc, s, blk, s)
+            sa = O.call("sa8d", idx, fenc, s, blk, s)
+            out[i]["sa8d"] += sa
+            if p == 0:
+                out[i]["psy"] = O.call("psy_cost_pp", idx, fenc, s, blk, s)
+                out[i]["sa8d_luma"] = sa
+                v = fenc.astype(np.int64)
+                mean = int(v.sum()) // (S * S)
+                out[i]["src_mean"] = mean
+                out[i]["src_homo"] = int(np.abs(v - mean).sum()) // (S * S)
+    return out
+
+
+MEASURE_KINDS = ("random", "both 0", "both pmax", "source pmax, tile 0", "checkerboard", "tile = source")
+MEASURE_W = 128
+
+
+def measure_case(depth, seed=1):
+    """CU measurement cases: a 128x128 source picture whose 64x64 quadrants hold noise | 0 / pmax | a 0 / pmax checkerboard of pitch 1 (chroma alike), and 72 CUs
+    -- every size 8..64 with every content of MEASURE_KINDS three times over, shuffled, at aligned positions of the quadrant that has their source -- each with
+    an RD_TILE (Y stride 64, U and V stride 32) whose samples outside the block carry a pattern.  CU 0 is the 64x64 CU of the largest difference a block can
+    have (source pmax against tile 0)."""
+    rng = np.random.default_rng(seed * 977 + depth)
+    dt = np.uint8 if depth == 8 else np.uint16
+    pmax = (1 << depth) - 1
+    W = MEASURE_W
+    src = []
+    for p in range(3):
+        w = W if p == 0 else W // 2
+        h = w // 2
+        yy, xx = np.mgrid[0:w, 0:w]
+        pl = rng.integers(0, pmax + 1, (w, w))
+        pl[:h, h:] = 0                                  # top right: 0
+        pl[h:, :h] = pmax                               # bottom left: pmax
+        pl[h:, h:] = ((yy + xx) & 1)[h:, h:] * pmax     # bottom right: checkerboard
+        src.append(np.ascontiguousarray(pl.astype(dt)))
+    combos = [(log2, k) for k in range(len(MEASURE_KINDS)) for log2 in (3, 4, 5, 6)] * 3
+    order = rng.permutation(len(combos))
+    combos = [combos[i] for i in order]
+    first = combos.index((6, 3))
+    combos[0], combos[first] = combos[first], combos[0]
+    n = len(combos)
+    cus = np.zeros(n, RD_CU_DT)
+    tiles = ((np.arange(n * RD_TILE, dtype=np.int64) * 7 + 3) % pmax + 1).astype(dt).reshape(n, RD_TILE)       # never 0: a sample read from outside the block shows
+    quadrant = {0: (0, 0), 1: (64, 0), 2: (0, 64), 3: (0, 64), 4: (64, 64), 5: (0, 0)}
+    for i, (log2, k) in enumerate(combos):
+        S = 1 << log2
+        qx, qy = quadrant[k]
+        x, y = qx + int(rng.integers(0, 64 // S)) * S, qy + int(rng.integers(0, 64 // S)) * S
+        cus[i]["x"], cus[i]["y"], cus[i]["log2_size"], cus[i]["qp"] = x, y, log2, 30
+        for p in range(3):
+            s, ts = (S, 64) if p == 0 else (S // 2, 32)
+            px, py = (x, y) if p == 0 else (x // 2, y // 2)
+            o = 0 if p == 0 else 4096 + (p - 1) * 1024
+            view = tiles[i][o:o + ts * ts].reshape(ts, ts)
+            blk = src[p][py:py + s, px:px + s]
+            if k == 0:
+                view[:s, :s] = rng.integers(0, pmax + 1, (s, s))
+            elif k in (1, 3):
+                view[:s, :s] = 0
+            elif k == 2:
+                view[:s, :s] = pmax
+            elif k == 4:
+                view[:s, :s] = pmax - blk       # the other colour of the board: +-pmax, alternating
+            else:
+                view[:s, :s] = blk
+    return dict(depth=depth, src=src, cus=cus, tiles=tiles, kinds=[k for _, k in combos], stride=W, cstride=W // 2)
+
+
+def cu_measure_run_hip(L, c, idx, stream=None, tile_list=False, seed=0):
+    """x265amd_measure_tiles (tile_list: x265amd_measure_tile_list with the tiles at shuffled addresses) on the CUs `idx` of a measure_case; returns
+    (records [n] CU_MEASURE_DT, tiles as they are afterwards [n, RD_TILE] in the order of idx, source planes as they are afterwards)"""
+    import torch
+    n = len(idx)
+    dt = c["tiles"].dtype
+    isz = dt.itemsize
+    cus = np.ascontiguousarray(c["cus"][idx])
+    place = np.random.default_rng(seed + n).permutation(n) if tile_list else np.arange(n)      # CU i's tile is the place[i]-th of the buffer
+    buf = np.zeros((n, RD_TILE), dt)
+    buf[place] = c["tiles"][idx]
+    d_src = [torch.from_numpy(np.ascontiguousarray(p).view(np.uint8).reshape(-1)).cuda() for p in c["src"]]
+    planes = np.array([d.data_ptr() for d in d_src], np.uint64)
+    d_tiles = torch.from_numpy(buf.view(np.uint8).reshape(-1)).cuda()
+    addrs = np.array([d_tiles.data_ptr() + int(k) * RD_TILE * isz for k in place], np.uint64)
+    out = np.zeros(n, CU_MEASURE_DT)
+    out["reserved"] = 0xFFFFFFFF
+    with stream_scope(stream) as st:
+        if tile_list:
+            rc = L.lib.x265amd_measure_tile_list(st, _ptr(planes), C.c_ssize_t(c["stride"]), C.c_ssize_t(c["cstride"]), _ptr(cus), n, _ptr(addrs), _ptr(out))
+        else:
+            rc = L.lib.x265amd_measure_tiles(st, _ptr(planes), C.c_ssize_t(c["stride"]), C.c_ssize_t(c["cstride"]), _ptr(cus), n, C.c_uint64(d_tiles.data_ptr()),
+                                             C.c_size_t(RD_TILE * isz), _ptr(out))
+    assert rc == 0, L.lib.x265amd_last_error()
+    back = d_tiles.cpu().numpy().view(dt).reshape(n, RD_TILE)[place].copy()
+    return out, back, [d.cpu().numpy().view(dt).reshape(p.shape) for d, p in zip(d_src, c["src"])]
+
+
 def _rd_layer_offset(plane, layer):
     return 4 * 4096 + ((layer - 2) * 2 + plane - 1) * 1024 if plane else (layer - 2) * 4096
 
@@ -2281,7 +2593,7 @@ def rd_compare(got, want, c, what):
             assert (gc[i][5120:5120 + S * S // 4] == wc[i][5120:5120 + S * S // 4]).all(), tag + ": V levels"
 
 
-def rd_run_hip(L, c):
+def rd_run_hip(L, c, stream=None):
     """x265amd_inter_residual_rd on the whole candidate list (one call); same return shape as rd_run_ref"""
     import torch
     n = len(c["cus"])
@@ -2296,7 +2608,7 @@ def rd_run_hip(L, c):
     cu_units = c["cu_units"].copy()
     out = np.zeros(n, RD_RESULT_DT)
     coeff = np.zeros((n, RD_TILE), np.int16)
-    with call_stream(L) as st_:
+    with (stream_scope(stream) if stream is not None else call_stream(L)) as st_:
         rc = L.lib.x265amd_inter_residual_rd(st_, _ptr(si), _ptr(c["rp"]), _ptr(units), _ptr(planes), C.c_ssize_t(c["width"]), C.c_ssize_t(c["width"] // 2),
                                              _ptr(c["cus"]), n, _ptr(cu_units), C.c_uint64(d_pred.data_ptr()), C.c_uint64(d_recon.data_ptr()),
                                              C.c_size_t(RD_TILE * isz), _ptr(out), _ptr(coeff))

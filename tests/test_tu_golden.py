@@ -58,42 +58,14 @@ def test_hip_transform_inverse(depth):
 @pytest.mark.parametrize("depth", [8, 10])
 def test_hip_tu_chain(depth):
     """the fused per-TU kernel (x265amd_tu_chain) on a batch, against the oracle's restatement of the measurement"""
-    import torch
     hip, orc = T.load_hip(depth), T.load_oracle(depth)
-    dt = np.uint8 if depth == 8 else np.uint16
     for seed in range(3):
         cases = T.tu_cases(depth, 300 + seed, 200)
         want = T.tu_run_chain_oracle(orc, cases)
-        # one arena: per case fenc | pred | coeff | resi | recon at stride 32
-        isz = np.dtype(dt).itemsize
-        per = 32 * 32 * (isz * 3 + 2 * 2)
-        arena = np.zeros(len(cases) * per, np.uint8)
-        jobs = np.zeros(len(cases), T.TU_JOB_DT)
-        for i, c in enumerate(cases):
-            N = 1 << c["log2"]
-            base = i * per
-            f = arena[base:base + 1024 * isz].view(dt).reshape(32, 32); f[:N, :N] = c["fenc"]
-            p = arena[base + 1024 * isz:base + 2048 * isz].view(dt).reshape(32, 32); p[:N, :N] = c["pred"]
-            jobs[i] = (0, 0, 0, 0, 0, 32, 32, 32, 32, c["log2"], c["ttype"], c["intra"], c["dir"], c["slice"], c["qp"], c["signhide"], 0)
-        d_arena = torch.from_numpy(arena).cuda()
-        a0 = d_arena.data_ptr()
-        for i in range(len(cases)):
-            base = a0 + i * per
-            jobs[i]["fenc"] = base; jobs[i]["pred"] = base + 1024 * isz
-            jobs[i]["recon"] = base + 2048 * isz; jobs[i]["coeff"] = base + 3072 * isz; jobs[i]["resi"] = base + 3072 * isz + 2048
-        d_jobs = torch.from_numpy(jobs.view(np.uint8).copy()).cuda()
-        d_out = torch.zeros(len(cases) * T.TU_RESULT_DT.itemsize, dtype=torch.uint8, device="cuda")
-        rc = hip.lib.x265amd_tu_chain(None, C.c_void_p(d_jobs.data_ptr()), len(cases), C.c_void_p(d_out.data_ptr()))
-        assert rc == 0
-        torch.cuda.synchronize()
-        res = d_out.cpu().numpy().view(T.TU_RESULT_DT)
-        back = d_arena.cpu().numpy()
-        for i, (c, w) in enumerate(zip(cases, want)):
-            N = 1 << c["log2"]
+        got = T.tu_chain_run_hip(hip, cases, depth)
+        for i, (c, w, g) in enumerate(zip(cases, want, got)):
             st, coeff, resi, recon = w
-            got = (int(res[i]["num_sig"]), int(res[i]["zero_dist"]), int(res[i]["zero_energy"]), int(res[i]["nz_dist"]), int(res[i]["nz_energy"]))
-            assert got == tuple(int(v) for v in st), (i, got, st)
-            base = i * per
-            assert np.array_equal(back[base + 2048 * isz:base + 3072 * isz].view(dt).reshape(32, 32)[:N, :N], recon), i
-            assert np.array_equal(back[base + 3072 * isz:base + 3072 * isz + N * N * 2].view(np.int16), coeff), i
-            assert np.array_equal(back[base + 3072 * isz + 2048:base + 3072 * isz + 4096].view(np.int16).reshape(32, 32)[:N, :N], resi), i
+            assert tuple(int(v) for v in g[0]) == tuple(int(v) for v in st), (i, g[0], st)
+            assert np.array_equal(g[3], recon), i
+            assert np.array_equal(g[1], coeff), i
+            assert np.array_equal(g[2], resi), i

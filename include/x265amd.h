@@ -143,6 +143,25 @@ void x265amd_chroma_p2s(int csp, int part, const pixel_t_* src, intptr_t srcStri
 /* ------------------------------------------------------------------------------------------------------- */
 /* Layer 2: batched job lists (DEVICE memory).                                                             */
 /* ------------------------------------------------------------------------------------------------------- */
+/* What a job may ask for (tests/test_job_lists.py runs batches that go as far as this and no further):
+ *  - Fields: `size`, p[], a..e and the strides are used per op exactly as the op's layer-1 entry point fills them
+ *    (csrc/slot_shims.hip); p[] holds the integer arguments in the order of the slot's typedef.
+ *  - Strides (sa, sb, sd) are in ELEMENTS of the operand's type and may have any value no smaller than the block
+ *    width, odd values included.  The operands with a stride are those with a stride argument in the slot's typedef;
+ *    weight_pp has one stride for source and destination (sa == sd).  sad_x3 / sad_x4 read fenc (a) at the
+ *    reference's FENC_STRIDE of 64 elements and take no stride for it; sb is the stride of all candidates.
+ *  - Packed operands (no stride, consecutive elements): the coefficient inputs of idct, idst4 and cpy1Dto2D_*; every
+ *    operand of quant, nquant, dequant_normal and dequant_scaling; the input of count_nonzero; the intra neighbour
+ *    arrays (4N + 1 samples) and the outputs of intra_filter and intra_allangs; the outputs of dct, dst4, cpy2Dto1D_*,
+ *    copy_cnt (coefficients), transpose, scale2D_64to32; both operands of scale1D_128to64.
+ *  - Alignment: operands need only the alignment of their element type (pixel, int16_t, int32_t), whatever the block
+ *    size.  The 64-bit scalar results -- d of the family-0 ops and of count_nonzero, e[0] of copy_cnt, e[1] of quant /
+ *    nquant -- are 8-byte aligned; the int32 results of sad_x3 / sad_x4 (d) are 4-byte aligned.
+ *  - Interpolation reads taps / 2 - 1 samples left of / above the block and taps - 1 - (taps / 2 - 1) right of / below it
+ *    in the filtered direction(s); hps with isRowExt also reads and writes those taps - 1 extra rows, starting
+ *    taps / 2 - 1 rows above `a` (d is the first extra row).
+ *  - A job writes its output block(s) and result word(s) and nothing else; jobs of one launch must not overlap in what
+ *    they write.  Any number of jobs, any mix of the family's ops and sizes, any stream. */
 enum x265amd_op
 {
     /* family 0: distortion.  a=fenc b=fref (device addresses), sa/sb strides in elements, d -> uint64 result

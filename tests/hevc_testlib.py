@@ -5082,3 +5082,663 @@ def filter_case_expected(O, P, c):
         sh = 1 if k else 0
         O.lib.orc_extend_pic_border(off(f.reshape(-1), c["org"][1 if k else 0]), C.c_int64(c["cstride"] if k else c["stride"]), w >> sh, h >> sh, mx >> sh, my >> sh)
     return dict(D=D, count=cnt, org=org, params=params, F=F)
+
+
+# ----------------------------------------------------------------------------------------------------------
+# layer 2 as documented (include/x265amd.h): batched job lists through x265amd_run_jobs -- tests/test_job_lists.py.
+# The per-slot shims (csrc/slot_shims.hip) repack every operand and launch one job; here the operands of a whole batch
+# lie in two arenas that exist twice, byte for byte: on the host, where the oracle runs on them, and on the device,
+# where the kernels do.  Job addresses are the device base plus the host offset and strides are the host's, so the whole
+# output arena can be compared at the end: every block right, nothing written outside one, nothing left unwritten.
+# ----------------------------------------------------------------------------------------------------------
+JOB_DT = np.dtype([("op", "<i4"), ("size", "<i4"), ("p", "<i4", (6,)), ("a", "<u8"), ("b", "<u8"), ("c", "<u8"), ("d", "<u8"), ("e", "<u8", (2,)),
+                   ("sa", "<i4"), ("sb", "<i4"), ("sc", "<i4"), ("sd", "<i4")])      # x265amd_job
+# enum x265amd_op; family = op // 32 (tests/test_job_lists.py checks the values against the header's text)
+JOB_OPS = dict(SAD=0, SAD_X3=1, SAD_X4=2, SATD=3, SA8D=4, SSE_PP=5, SSE_SS=6, SSD_S=7, PSY_COST_PP=8, VAR=9, CHROMA_SATD=10, CHROMA_SA8D=11,
+               SUB_PS=32, ADD_PS=33, PIXELAVG_PP=34, ADDAVG=35, WEIGHT_PP=36, WEIGHT_SP=37, SCALE2D_64TO32=38, SCALE1D_128TO64=39, TRANSPOSE=40,
+               CPY2DTO1D_SHL=41, CPY2DTO1D_SHR=42, CPY1DTO2D_SHL=43, CPY1DTO2D_SHR=44, COPY_CNT=45, COUNT_NONZERO=46,
+               DCT=64, IDCT=65, DST4=66, IDST4=67, QUANT=68, NQUANT=69, DEQUANT_NORMAL=70, DEQUANT_SCALING=71,
+               INTRA_PRED=96, INTRA_FILTER=97, INTRA_ALLANGS=98,
+               IP_HPP=128, IP_HPS=129, IP_VPP=130, IP_VPS=131, IP_VSP=132, IP_VSS=133, IP_HVPP=134, IP_P2S=135)
+JOB_OP_NAME = {v: k for k, v in JOB_OPS.items()}
+JOB_FAMILIES = 5
+# how many distinct (size index, filter phase ...) keys every op has to appear with over a family's batches:
+#   PU ops 25 partitions, CU ops 5 sizes (TU ops 4); chroma_satd the 18 partitions whose 4:2:0 half is a multiple of 4x4, chroma_sa8d cu 1..4;
+#   addAvg luma + 4:2:0; weight_pp widths 16..64 in steps of 16, weight_sp those less one; quantisation 16 / 64 / 256 / 1024 coefficients;
+#   intra_pred 4 sizes x 35 modes x bFilter, allangs 4 sizes x bLuma;
+#   interpolation: luma 25 partitions x coeffIdx 0..3, 4:2:0 chroma 24 partitions (none for part 0) x coeffIdx 0..7; hps twice that (isRowExt); hvpp 25 x the nine
+#   (idxX, idxY) in 1..3 x 1..3; p2s 25 + 24
+JOB_COVERAGE = dict(SAD=25, SAD_X3=25, SAD_X4=25, SATD=25, SA8D=5, SSE_PP=5, SSE_SS=5, SSD_S=5, PSY_COST_PP=5, VAR=5, CHROMA_SATD=18, CHROMA_SA8D=4,
+                    SUB_PS=5, ADD_PS=5, PIXELAVG_PP=25, ADDAVG=50, WEIGHT_PP=4, WEIGHT_SP=4, SCALE2D_64TO32=1, SCALE1D_128TO64=1, TRANSPOSE=5,
+                    CPY2DTO1D_SHL=4, CPY2DTO1D_SHR=4, CPY1DTO2D_SHL=4, CPY1DTO2D_SHR=4, COPY_CNT=4, COUNT_NONZERO=4,
+                    DCT=4, IDCT=4, DST4=1, IDST4=1, QUANT=4, NQUANT=4, DEQUANT_NORMAL=4, DEQUANT_SCALING=4,
+                    INTRA_PRED=280, INTRA_FILTER=4, INTRA_ALLANGS=8,
+                    IP_HPP=25 * 4 + 24 * 8, IP_HPS=2 * (25 * 4 + 24 * 8), IP_VPP=25 * 4 + 24 * 8, IP_VPS=25 * 4 + 24 * 8, IP_VSP=25 * 4 + 24 * 8,
+                    IP_VSS=25 * 4 + 24 * 8, IP_HVPP=25 * 9, IP_P2S=25 + 24)
+JOB_PLANE = 8192            # elements per shared source plane: the largest reach is an 8-tap 64x64 block at stride 83, (63 + 7) * 83 + 64 + 7 elements
+JOB_GUARD = 8               # poison bytes kept between two jobs' output regions, at least
+
+
+class _JobHost:
+    """pointers into the host copies of the two arenas, for the oracle side of a job"""
+
+    def __init__(self, inb, outb):
+        self.inb, self.outb = inb, outb
+
+    def i(self, o):
+        return C.c_void_p(self.inb.ctypes.data + o)
+
+    def o(self, o):
+        return C.c_void_p(self.outb.ctypes.data + o)
+
+    def u64(self, o, v):
+        """a scalar result as the kernels store it: the int (sign-extended) or uint64 return value in a 64-bit word"""
+        self.outb[o:o + 8] = np.array([int(v) & 0xFFFFFFFFFFFFFFFF], np.uint64).view(np.uint8)
+
+
+class JobSpec:
+    """one job before the device addresses are known: ins / outs map the record's address fields (a b c d e0 e1) to byte offsets in the input / output arena"""
+    __slots__ = ("op", "size", "p", "ins", "outs", "sa", "sb", "sc", "sd", "key", "oracle")
+
+    def name(self):
+        return "%s size %d key %s" % (JOB_OP_NAME[self.op], self.size, self.key)
+
+
+class JobArena:
+    """The memory of one family's jobs for one (depth, mode).  Input: a few shared source planes (pix_buf / s16_buf contents and ranges of the case_* functions above) that
+    the jobs read at their own offsets, as the calls of a host loop read one picture.  Output: a disjoint region per job, handed out by a cursor while the jobs are built.
+    The j_* methods are the builders, one per op; each follows the op's shim in csrc/slot_shims.hip field for field and returns the JobSpec whose `oracle` is the orc_* call
+    with the same size index, pointers and strides on the host copies."""
+
+    def __init__(self, L, rng, mode):
+        self.L, self.rng, self.mode, self.px = L, rng, mode, np.dtype(L.pixel).itemsize
+        opp = "random" if mode == "random" else ("max" if mode == "min" else "min")
+        lim, n = L.pmax, JOB_PLANE
+        self.rem = int(rng.integers(0, 6))          # qp % 6 of the quantisation tables in this arena
+        smooth = np.clip(np.cumsum(rng.integers(-3, 4, n)) + L.pmax // 2, 0, L.pmax).astype(L.pixel) if mode == "random" else pix_buf(L, rng, n, mode)
+        qc = np.full(n, QUANT_SCALES[self.rem], np.int32)
+        dqc = np.full(n, INV_QUANT_SCALES[self.rem] * 16, np.int32)
+        if mode == "random":                        # scaling-list style tables, as in case_quant
+            qc = (qc.astype(np.int64) * 16 // rng.integers(8, 40, n)).astype(np.int32)
+            dqc = (INV_QUANT_SCALES[self.rem] * rng.integers(8, 40, n)).astype(np.int32)
+        planes = [("pix", pix_buf(L, rng, n, mode)), ("pix2", pix_buf(L, rng, n, opp)), ("smooth", smooth),
+                  ("res", s16_buf(rng, n, -lim, lim, mode)), ("res2", s16_buf(rng, n, -lim, lim, opp)),
+                  ("ifs", s16_buf(rng, n, -8192, 8191, mode)), ("coef", s16_buf(rng, n, -32768, 32767, mode)),
+                  ("cpy", s16_buf(rng, n, -4096, 4095, mode)), ("lvl", s16_buf(rng, n, -3, 3, mode)), ("qc", qc), ("dqc", dqc)]
+        self.planes, parts, at = {}, [], 0
+        for kind, arr in planes:
+            self.planes[kind] = (at, arr.itemsize)
+            raw = arr.view(np.uint8)
+            parts.append(raw)
+            pad = -raw.size % 64
+            parts.append(np.zeros(pad, np.uint8))
+            at += raw.size + pad
+        self.inb = np.concatenate(parts)
+        self.cur = 0
+        self.specs = []
+
+    # ---- placement ----
+    def stride(self, w):
+        """the block width itself, the width plus a small even padding, or an odd stride"""
+        return int(self.rng.choice([w, w + 2, w + 6, w + 16, 67, 83]))
+
+    def pick(self, kind, before, after):
+        """byte offset of an operand in the shared plane `kind`: an odd element offset that leaves `before` elements in front of it and `after` from it on"""
+        at, elem = self.planes[kind]
+        lo, hi = before, JOB_PLANE - after
+        assert 0 <= lo < hi - 1, (kind, before, after)
+        o = int(self.rng.integers(lo, hi)) | 1
+        if o > hi:
+            o -= 2
+        assert lo <= o <= hi and o & 1
+        return at + o * elem
+
+    def _out(self, nbytes, skew):
+        start = (self.cur + JOB_GUARD + 7) // 8 * 8 + skew
+        self.cur = start + nbytes
+        return start
+
+    def out_rect(self, elem, w, h, stride):
+        """an output block: element-aligned, at an odd element offset from an 8-byte boundary"""
+        return self._out(((h - 1) * stride + w) * elem, elem * int(self.rng.choice([1, 3])))
+
+    def out_flat(self, elem, n):
+        return self.out_rect(elem, n, 1, n)
+
+    def out_u64(self):
+        return self._out(8, 0)                      # 64-bit scalar results: 8-byte aligned
+
+    def out_i32(self, n):
+        return self._out(4 * n, 4)                  # sad_x3 / sad_x4 results: 4-byte aligned and no more
+
+    @property
+    def out_size(self):
+        return (self.cur + JOB_GUARD + 63) // 64 * 64
+
+    def poison(self):
+        return ((np.arange(self.out_size, dtype=np.uint32) * 37 + 11) & 0xFF).astype(np.uint8)
+
+    def job(self, op, size, key, oracle, p=(), ins=None, outs=None, sa=0, sb=0, sc=0, sd=0):
+        s = JobSpec()
+        s.op, s.size, s.key, s.oracle = JOB_OPS[op], size, key, oracle
+        s.p = tuple(p) + (0,) * (6 - len(p))
+        s.ins, s.outs, s.sa, s.sb, s.sc, s.sd = ins or {}, outs or {}, sa, sb, sc, sd
+        self.specs.append(s)
+        return s
+
+    # ---- family 0: distortion (dist_pp, sad_xn and the 16-bit forms of the shims) ----
+    def _dist(self, op, name, size, w, h, kinds=("pix", "pix2"), csp=False):
+        sa, sb = self.stride(w), self.stride(w)
+        a, b, d = self.pick(kinds[0], 0, (h - 1) * sa + w), self.pick(kinds[1], 0, (h - 1) * sb + w), self.out_u64()
+        args = (CSP_I420, size) if csp else (size,)
+        return self.job(op, size, (size,), lambda O, M: M.u64(d, O.call(name, *args, M.i(a), sa, M.i(b), sb)), ins=dict(a=a, b=b), outs=dict(d=d), sa=sa, sb=sb)
+
+    def _dist1(self, op, name, size, kind):
+        n = 4 << size
+        sa = self.stride(n)
+        a, d = self.pick(kind, 0, (n - 1) * sa + n), self.out_u64()
+        return self.job(op, size, (size,), lambda O, M: M.u64(d, O.call(name, size, M.i(a), sa)), ins=dict(a=a), outs=dict(d=d), sa=sa)
+
+    def _sad_xn(self, op, name, part, nc):
+        w, h = PU_SIZES[part]
+        sb = self.stride(w)
+        a = self.pick("pix", 0, (h - 1) * FENC_STRIDE + w)          # fenc: the reference's 64-element stride, no stride field
+        r = [self.pick("pix2", 0, (h - 1) * sb + w) for _ in range(nc)]
+        d = self.out_i32(nc)
+        ins = dict(zip(("b", "c", "e0", "e1"), r), a=a)
+        return self.job(op, part, (part,), lambda O, M: O.call(name, part, M.i(a), *[M.i(x) for x in r], sb, M.o(d)), ins=ins, outs=dict(d=d), sb=sb)
+
+    def j_sad(self, part): return self._dist("SAD", "sad", part, *PU_SIZES[part])
+    def j_sad_x3(self, part): return self._sad_xn("SAD_X3", "sad_x3", part, 3)
+    def j_sad_x4(self, part): return self._sad_xn("SAD_X4", "sad_x4", part, 4)
+    def j_satd(self, part): return self._dist("SATD", "satd", part, *PU_SIZES[part])
+    def j_sa8d(self, cu): return self._dist("SA8D", "sa8d", cu, 4 << cu, 4 << cu)
+    def j_sse_pp(self, cu): return self._dist("SSE_PP", "sse_pp", cu, 4 << cu, 4 << cu)
+    def j_sse_ss(self, cu): return self._dist("SSE_SS", "sse_ss", cu, 4 << cu, 4 << cu, kinds=("res", "res2"))
+    def j_ssd_s(self, cu): return self._dist1("SSD_S", "ssd_s", cu, "res")
+    def j_psy_cost_pp(self, cu): return self._dist("PSY_COST_PP", "psy_cost_pp", cu, 4 << cu, 4 << cu)
+    def j_var(self, cu): return self._dist1("VAR", "var", cu, "pix")
+    def j_chroma_satd(self, part): return self._dist("CHROMA_SATD", "chroma_satd", part, PU_SIZES[part][0] // 2, PU_SIZES[part][1] // 2, csp=True)
+    def j_chroma_sa8d(self, cu): return self._dist("CHROMA_SA8D", "chroma_sa8d", cu, 2 << cu, 2 << cu, csp=True)
+
+    # ---- family 1: pixel / residual block ops ----
+    def _rect3(self, op, size, key, w, h, ka, ea, kb, eb, ed, call, p=()):
+        """two strided inputs, one strided output"""
+        sa, sb, sd = self.stride(w), self.stride(w), self.stride(w)
+        a, b, d = self.pick(ka, 0, (h - 1) * sa + w), self.pick(kb, 0, (h - 1) * sb + w), self.out_rect(ed, w, h, sd)
+        return self.job(op, size, key, lambda O, M: call(O, M.i(a), sa, M.i(b), sb, M.o(d), sd), p=p, ins=dict(a=a, b=b), outs=dict(d=d), sa=sa, sb=sb, sd=sd)
+
+    def j_sub_ps(self, cu):
+        n = 4 << cu
+        return self._rect3("SUB_PS", cu, (cu,), n, n, "pix", self.px, "pix2", self.px, 2, lambda O, a, sa, b, sb, d, sd: O.call("sub_ps", cu, d, sd, a, b, sa, sb))
+
+    def j_add_ps(self, cu):
+        n = 4 << cu
+        return self._rect3("ADD_PS", cu, (cu,), n, n, "pix", self.px, "res", 2, self.px, lambda O, a, sa, b, sb, d, sd: O.call("add_ps", cu, d, sd, a, b, sa, sb))
+
+    def j_pixelavg_pp(self, part):
+        w, h = PU_SIZES[part]
+        return self._rect3("PIXELAVG_PP", part, (part,), w, h, "pix", self.px, "pix", self.px, self.px, lambda O, a, sa, b, sb, d, sd: O.call("pixelavg_pp", part, d, sd, a, sa, b, sb))
+
+    def j_addavg(self, part, chroma):
+        w, h = PU_SIZES[part][0] >> chroma, PU_SIZES[part][1] >> chroma
+        if chroma:
+            call = lambda O, a, sa, b, sb, d, sd: O.call("chroma_addAvg", CSP_I420, part, a, b, d, sa, sb, sd)
+        else:
+            call = lambda O, a, sa, b, sb, d, sd: O.call("addAvg", part, a, b, d, sa, sb, sd)
+        return self._rect3("ADDAVG", part, (part, chroma), w, h, "ifs", 2, "ifs", 2, self.px, call, p=(chroma,))
+
+    def _weight_args(self):
+        rng, corr = self.rng, 14 - self.L.depth
+        shift = int(rng.integers(0, 7)) + corr
+        rnd = ((1 << (shift - 1)) if shift else 0) & ~((1 << corr) - 1)
+        return int(rng.integers(1, 17)), int(rng.integers(1, 128)), rnd, shift, int(rng.integers(-20, 21))
+
+    def j_weight_pp(self, w):
+        """w: a multiple of 16.  weightp_pp_t has ONE stride for source and destination: sa == sd"""
+        h, w0, rnd, shift, offset = self._weight_args()
+        st = self.stride(w)
+        a, d = self.pick("pix", 0, (h - 1) * st + w), self.out_rect(self.px, w, h, st)
+        return self.job("WEIGHT_PP", 0, (w,), lambda O, M: O.call("weight_pp", M.i(a), M.o(d), st, w, h, w0, rnd, shift, offset), p=(w, h, w0, rnd, shift, offset),
+                        ins=dict(a=a), outs=dict(d=d), sa=st, sd=st)
+
+    def j_weight_sp(self, w):
+        h, w0, rnd, shift, offset = self._weight_args()
+        sa, sd = self.stride(w), self.stride(w)
+        a, d = self.pick("ifs", 0, (h - 1) * sa + w), self.out_rect(self.px, w, h, sd)
+        return self.job("WEIGHT_SP", 0, (w,), lambda O, M: O.call("weight_sp", M.i(a), M.o(d), sa, sd, w, h, w0, rnd, shift, offset), p=(w, h, w0, rnd, shift, offset),
+                        ins=dict(a=a), outs=dict(d=d), sa=sa, sd=sd)
+
+    def j_scale2d_64to32(self):
+        sa = self.stride(64)
+        a, d = self.pick("pix", 0, 63 * sa + 64), self.out_flat(self.px, 32 * 32)
+        return self.job("SCALE2D_64TO32", 0, (0,), lambda O, M: O.call("scale2D_64to32", M.o(d), M.i(a), sa), ins=dict(a=a), outs=dict(d=d), sa=sa)
+
+    def j_scale1d_128to64(self):
+        a, d = self.pick("pix", 0, 256), self.out_flat(self.px, 128)
+        return self.job("SCALE1D_128TO64", 0, (0,), lambda O, M: O.call("scale1D_128to64", M.o(d), M.i(a)), ins=dict(a=a), outs=dict(d=d))
+
+    def j_transpose(self, cu):
+        n = 4 << cu
+        sa = self.stride(n)
+        a, d = self.pick("pix", 0, (n - 1) * sa + n), self.out_flat(self.px, n * n)
+        return self.job("TRANSPOSE", cu, (cu,), lambda O, M: O.call("transpose", cu, M.o(d), M.i(a), sa), ins=dict(a=a), outs=dict(d=d), sa=sa)
+
+    def _cpy(self, op, name, cu, to1d):
+        n, shift = 4 << cu, int(self.rng.integers(1, 3))
+        st = self.stride(n)
+        if to1d:
+            a, d = self.pick("cpy", 0, (n - 1) * st + n), self.out_flat(2, n * n)
+            return self.job(op, cu, (cu,), lambda O, M: O.call(name, cu, M.o(d), M.i(a), st, shift), p=(shift,), ins=dict(a=a), outs=dict(d=d), sa=st)
+        a, d = self.pick("cpy", 0, n * n), self.out_rect(2, n, n, st)           # the coefficient input is packed
+        return self.job(op, cu, (cu,), lambda O, M: O.call(name, cu, M.o(d), M.i(a), st, shift), p=(shift,), ins=dict(a=a), outs=dict(d=d), sd=st)
+
+    def j_cpy2dto1d_shl(self, cu): return self._cpy("CPY2DTO1D_SHL", "cpy2Dto1D_shl", cu, True)
+    def j_cpy2dto1d_shr(self, cu): return self._cpy("CPY2DTO1D_SHR", "cpy2Dto1D_shr", cu, True)
+    def j_cpy1dto2d_shl(self, cu): return self._cpy("CPY1DTO2D_SHL", "cpy1Dto2D_shl", cu, False)
+    def j_cpy1dto2d_shr(self, cu): return self._cpy("CPY1DTO2D_SHR", "cpy1Dto2D_shr", cu, False)
+
+    def j_copy_cnt(self, cu):
+        n = 4 << cu
+        sa = self.stride(n)
+        a, d, e0 = self.pick("lvl" if self.rng.integers(0, 2) else "cpy", 0, (n - 1) * sa + n), self.out_flat(2, n * n), self.out_u64()
+        return self.job("COPY_CNT", cu, (cu,), lambda O, M: M.u64(e0, O.call("copy_cnt", cu, M.o(d), M.i(a), sa)), ins=dict(a=a), outs=dict(d=d, e0=e0), sa=sa)
+
+    def j_count_nonzero(self, cu):
+        n = 4 << cu
+        a, d = self.pick("lvl", 0, n * n), self.out_u64()                       # packed
+        return self.job("COUNT_NONZERO", cu, (cu,), lambda O, M: M.u64(d, O.call("count_nonzero", cu, M.i(a))), ins=dict(a=a), outs=dict(d=d))
+
+    # ---- family 2: transforms + quantisation ----
+    def _fwd(self, op, name, cu, dst4):
+        n = 4 << cu
+        sa = self.stride(n)
+        a, d = self.pick("res", 0, (n - 1) * sa + n), self.out_flat(2, n * n)
+        call = (lambda O, M: O.call(name, M.i(a), M.o(d), sa)) if dst4 else (lambda O, M: O.call(name, cu, M.i(a), M.o(d), sa))
+        return self.job(op, cu, (cu,), call, ins=dict(a=a), outs=dict(d=d), sa=sa)
+
+    def _inv(self, op, name, cu, dst4):
+        """coefficients packed; plausible (residual-range) or full-range values, as case_dct feeds both"""
+        n = 4 << cu
+        sd = self.stride(n)
+        a, d = self.pick("coef" if self.rng.integers(0, 2) else "res", 0, n * n), self.out_rect(2, n, n, sd)
+        call = (lambda O, M: O.call(name, M.i(a), M.o(d), sd)) if dst4 else (lambda O, M: O.call(name, cu, M.i(a), M.o(d), sd))
+        return self.job(op, cu, (cu,), call, ins=dict(a=a), outs=dict(d=d), sd=sd)
+
+    def j_dct(self, cu): return self._fwd("DCT", "dct", cu, False)
+    def j_idct(self, cu): return self._inv("IDCT", "idct", cu, False)
+    def j_dst4(self): return self._fwd("DST4", "dst4x4", 0, True)
+    def j_idst4(self): return self._inv("IDST4", "idst4x4", 0, True)
+
+    def _qparams(self, cu):
+        """qBits / add / per / dequantisation shift of case_quant for a TU of size index cu, at a QP whose remainder is the arena's"""
+        per = int(self.rng.integers(0, 9 if self.rem < 4 else 8))
+        tshift = 15 - self.L.depth - (cu + 2)
+        qbits = 14 + per + tshift
+        return qbits, (171 if self.rng.integers(0, 2) else 85) << (qbits - 9), per, 20 - 14 - tshift
+
+    def j_quant(self, cu):
+        num = (4 << cu) ** 2
+        qbits, add, _, _ = self._qparams(cu)
+        a, b = self.pick("coef", 0, num), self.pick("qc", 0, num)
+        d, e0, e1 = self.out_flat(2, num), self.out_flat(4, num), self.out_u64()
+        return self.job("QUANT", 0, (num,), lambda O, M: M.u64(e1, O.call("quant", M.i(a), M.i(b), M.o(e0), M.o(d), qbits, add, num)), p=(qbits, add, num),
+                        ins=dict(a=a, b=b), outs=dict(d=d, e0=e0, e1=e1))
+
+    def j_nquant(self, cu):
+        num = (4 << cu) ** 2
+        qbits, add, _, _ = self._qparams(cu)
+        a, b, d, e1 = self.pick("coef", 0, num), self.pick("qc", 0, num), self.out_flat(2, num), self.out_u64()
+        return self.job("NQUANT", 0, (num,), lambda O, M: M.u64(e1, O.call("nquant", M.i(a), M.i(b), M.o(d), qbits, add, num)), p=(qbits, add, num),
+                        ins=dict(a=a, b=b), outs=dict(d=d, e1=e1))
+
+    def j_dequant_normal(self, cu):
+        num = (4 << cu) ** 2
+        _, _, per, shift = self._qparams(cu)
+        scale = INV_QUANT_SCALES[self.rem] << per
+        a, d = self.pick("coef", 0, num), self.out_flat(2, num)
+        return self.job("DEQUANT_NORMAL", 0, (num,), lambda O, M: O.call("dequant_normal", M.i(a), M.o(d), num, scale, shift), p=(num, scale, shift), ins=dict(a=a), outs=dict(d=d))
+
+    def j_dequant_scaling(self, cu):
+        num = (4 << cu) ** 2
+        _, _, per, shift = self._qparams(cu)
+        a, b, d = self.pick("coef", 0, num), self.pick("dqc", 0, num), self.out_flat(2, num)
+        return self.job("DEQUANT_SCALING", 0, (num,), lambda O, M: O.call("dequant_scaling", M.i(a), M.i(b), M.o(d), num, per, shift), p=(num, per, shift),
+                        ins=dict(a=a, b=b), outs=dict(d=d))
+
+    # ---- family 3: intra prediction (neighbour arrays packed: 4N + 1 samples) ----
+    def j_intra_pred(self, cu, mode, bfilter):
+        n = 4 << cu
+        sd = self.stride(n)
+        a, d = self.pick("smooth" if self.rng.integers(0, 2) else "pix", 0, 4 * n + 1), self.out_rect(self.px, n, n, sd)
+        return self.job("INTRA_PRED", cu, (cu, mode, bfilter), lambda O, M: O.call("intra_pred", cu, mode, M.o(d), sd, M.i(a), bfilter), p=(mode, bfilter),
+                        ins=dict(a=a), outs=dict(d=d), sd=sd)
+
+    def j_intra_filter(self, cu):
+        n = 4 << cu
+        a, d = self.pick("smooth" if self.rng.integers(0, 2) else "pix", 0, 4 * n + 1), self.out_flat(self.px, 4 * n + 1)
+        return self.job("INTRA_FILTER", cu, (cu,), lambda O, M: O.call("intra_filter", cu, M.i(a), M.o(d)), ins=dict(a=a), outs=dict(d=d))
+
+    def j_intra_allangs(self, cu, bluma):
+        n = 4 << cu
+        a, b, d = self.pick("pix", 0, 4 * n + 1), self.pick("smooth", 0, 4 * n + 1), self.out_flat(self.px, 33 * n * n)
+        return self.job("INTRA_ALLANGS", cu, (cu, bluma), lambda O, M: O.call("intra_allangs", cu, M.o(d), M.i(a), M.i(b), bluma), p=(bluma,), ins=dict(a=a, b=b), outs=dict(d=d))
+
+    # ---- family 4: interpolation.  The margins are those of the shim's interp(): taps / 2 - 1 samples left and above, taps - 1 - (taps / 2 - 1) right and below ----
+    def _ip(self, op, name, part, chroma, idx, aux, horiz, vert, src16, dst16, ext_rows=0, extra=None):
+        taps = 4 if chroma else 8
+        w, h = PU_SIZES[part][0] >> chroma, PU_SIZES[part][1] >> chroma
+        half = taps // 2 - 1
+        mx, mxr = (half, taps - 1 - half) if horiz else (0, 0)
+        mt, mb = (half, taps - 1 - half) if vert else (0, 0)
+        sa, sd = self.stride(w), self.stride(w)
+        a = self.pick("ifs" if src16 else "pix", mt * sa + mx, (h - 1 + mb) * sa + w + mxr)
+        d = self.out_rect(2 if dst16 else self.px, w, h + ext_rows, sd)
+        args = ((CSP_I420, part) if chroma else (part,))
+        tail = () if extra is None else extra
+        return self.job(op, 0, (part, chroma) + tuple(tail), lambda O, M: O.call(("chroma_" if chroma else "luma_") + name, *args, M.i(a), sa, M.o(d), sd, *tail),
+                        p=(taps, w, h, idx, aux), ins=dict(a=a), outs=dict(d=d), sa=sa, sd=sd)
+
+    def j_ip_hpp(self, part, chroma, idx): return self._ip("IP_HPP", "hpp", part, chroma, idx, 0, True, False, False, False, extra=(idx,))
+    def j_ip_hps(self, part, chroma, idx, ext):
+        return self._ip("IP_HPS", "hps", part, chroma, idx, ext, True, ext != 0, False, True, ext_rows=((3 if chroma else 7) if ext else 0), extra=(idx, ext))
+    def j_ip_vpp(self, part, chroma, idx): return self._ip("IP_VPP", "vpp", part, chroma, idx, 0, False, True, False, False, extra=(idx,))
+    def j_ip_vps(self, part, chroma, idx): return self._ip("IP_VPS", "vps", part, chroma, idx, 0, False, True, False, True, extra=(idx,))
+    def j_ip_vsp(self, part, chroma, idx): return self._ip("IP_VSP", "vsp", part, chroma, idx, 0, False, True, True, False, extra=(idx,))
+    def j_ip_vss(self, part, chroma, idx): return self._ip("IP_VSS", "vss", part, chroma, idx, 0, False, True, True, True, extra=(idx,))
+    def j_ip_hvpp(self, part, ix, iy): return self._ip("IP_HVPP", "hvpp", part, 0, ix, iy, True, True, False, False, extra=(ix, iy))
+    def j_ip_p2s(self, part, chroma): return self._ip("IP_P2S", "p2s", part, chroma, 0, 0, False, False, False, True)
+
+
+def chroma_satd_defined(part):
+    """the 4:2:0 half of the partition is a multiple of 4x4 (reference: pixel.cpp:1205-1229; NULL slots otherwise)"""
+    return ((PU_SIZES[part][0] >> 1) | (PU_SIZES[part][1] >> 1)) & 3 == 0
+
+
+def job_family_specs(L, family, mode, seed):
+    """JobArena with every (op, size index, filter phase) of the family built, families 0..3 several times over with fresh strides and offsets; arena.specs shuffled"""
+    rng = np.random.default_rng(case_seed("jobs%d" % family, L.depth, mode, seed))
+    A = JobArena(L, rng, mode)
+    parts, cus, tus = range(25), range(5), range(4)
+    if family == 0:
+        for _ in range(3):
+            for part in parts:
+                A.j_sad(part); A.j_sad_x3(part); A.j_sad_x4(part); A.j_satd(part)
+                if chroma_satd_defined(part):
+                    A.j_chroma_satd(part)
+            for cu in cus:
+                A.j_sa8d(cu); A.j_sse_pp(cu); A.j_sse_ss(cu); A.j_ssd_s(cu); A.j_psy_cost_pp(cu); A.j_var(cu)
+                if cu >= 1:
+                    A.j_chroma_sa8d(cu)
+    elif family == 1:
+        for _ in range(3):
+            for part in parts:
+                A.j_pixelavg_pp(part); A.j_addavg(part, 0); A.j_addavg(part, 1)
+            for cu in cus:
+                A.j_sub_ps(cu); A.j_add_ps(cu); A.j_transpose(cu)
+            for cu in tus:
+                A.j_cpy2dto1d_shl(cu); A.j_cpy2dto1d_shr(cu); A.j_cpy1dto2d_shl(cu); A.j_cpy1dto2d_shr(cu); A.j_copy_cnt(cu); A.j_count_nonzero(cu)
+            for w in (16, 32, 48, 64):
+                A.j_weight_pp(w); A.j_weight_sp(w - 1)
+            A.j_scale2d_64to32(); A.j_scale1d_128to64()
+    elif family == 2:
+        for _ in range(8):
+            for cu in tus:
+                A.j_quant(cu); A.j_nquant(cu); A.j_dequant_normal(cu); A.j_dequant_scaling(cu)
+                for _ in range(3):      # the transforms are the ops with per-wave LDS: most blocks of the shuffled batch should hold several of them
+                    A.j_dct(cu); A.j_idct(cu)
+            A.j_dst4(); A.j_idst4(); A.j_dst4(); A.j_idst4()
+    elif family == 3:
+        for cu in tus:
+            for m in range(35):
+                for bf in (0, 1):
+                    A.j_intra_pred(cu, m, bf)
+            for _ in range(3):
+                A.j_intra_filter(cu); A.j_intra_allangs(cu, 0); A.j_intra_allangs(cu, 1)
+    elif family == 4:
+        for part in parts:
+            for chroma in ((0, 1) if part else (0,)):       # no 2x2 chroma filters (reference: ipfilter.cpp:418-466)
+                for idx in range(8 if chroma else 4):
+                    A.j_ip_hpp(part, chroma, idx); A.j_ip_hps(part, chroma, idx, 0); A.j_ip_hps(part, chroma, idx, 1)
+                    A.j_ip_vpp(part, chroma, idx); A.j_ip_vps(part, chroma, idx); A.j_ip_vsp(part, chroma, idx); A.j_ip_vss(part, chroma, idx)
+                A.j_ip_p2s(part, chroma)
+            for ix in (1, 2, 3):
+                for iy in (1, 2, 3):
+                    A.j_ip_hvpp(part, ix, iy)
+    else:
+        raise ValueError(family)
+    order = rng.permutation(len(A.specs))
+    A.specs = [A.specs[i] for i in order]
+    return A
+
+
+def job_coverage(specs):
+    """{op name: number of distinct keys}"""
+    seen = {}
+    for s in specs:
+        seen.setdefault(JOB_OP_NAME[s.op], set()).add(s.key)
+    return {k: len(v) for k, v in seen.items()}
+
+
+def job_mixed_head(specs, n):
+    """n jobs of as many different ops as the list offers, in list order but the ops with per-wave LDS (the transforms) first: the small batches, so that the
+    waves of the one or two blocks hold different ops and, in family 2, more than one LDS region is in use"""
+    lds = {JOB_OPS[k] for k in ("DCT", "IDCT", "DST4", "IDST4")}
+    specs = sorted(specs, key=lambda s: s.op not in lds)
+    head, ops = [], set()
+    for s in specs:
+        if s.op not in ops:
+            head.append(s); ops.add(s.op)
+        if len(head) == n:
+            return head
+    return head + [s for s in specs if s not in head][:n - len(head)]
+
+
+def job_records(specs, in_base, out_base):
+    recs = np.zeros(len(specs), JOB_DT)
+    for r, s in zip(recs, specs):
+        r["op"], r["size"], r["p"], r["sa"], r["sb"], r["sc"], r["sd"] = s.op, s.size, s.p, s.sa, s.sb, s.sc, s.sd
+        for base, fields in ((in_base, s.ins), (out_base, s.outs)):
+            for f, o in fields.items():
+                if f in ("e0", "e1"):
+                    r["e"][int(f[1])] = base + o
+                else:
+                    r[f] = base + o
+    return recs
+
+
+def job_touch(r, depth):
+    """Every address range the kernels of csrc/prim_kernels.hip can touch for the record r, from the record alone: [(first byte, one past the last, is a write)].
+    The interpolation ranges are those of the shim's interp(): taps / 2 - 1 samples left and above, taps - 1 - (taps / 2 - 1) right and below, the taps - 1 extra
+    rows of hps with isRowExt; sad_x3 / sad_x4 read fenc at the reference's 64-element stride."""
+    px = 1 if depth == 8 else 2
+    op, size, p = JOB_OP_NAME[int(r["op"])], int(r["size"]), [int(v) for v in r["p"]]
+    a, b, c, d, e0, e1 = [int(r[f]) for f in "abcd"] + [int(r["e"][0]), int(r["e"][1])]
+    sa, sb, sd = int(r["sa"]), int(r["sb"]), int(r["sd"])
+    out = []
+
+    def rect(addr, elem, w, h, stride, write=False, block_w=None):
+        block_w = w if block_w is None else block_w
+        assert stride >= block_w or h == 1, (op, stride, block_w)       # the contract: strides no smaller than the block width
+        out.append((addr, addr + ((h - 1) * stride + w) * elem, write))
+
+    def flat(addr, nbytes, write=False):
+        out.append((addr, addr + nbytes, write))
+
+    if op in ("SAD", "SAD_X3", "SAD_X4", "SATD", "CHROMA_SATD", "PIXELAVG_PP", "ADDAVG"):
+        assert 0 <= size < 25       # the kernels look the partition up in a table of 25
+    else:
+        assert 0 <= size < 5
+    W, H = PU_SIZES[size]
+    N = 4 << size
+    if op in ("SAD", "SATD", "CHROMA_SATD"):
+        w, h = (W // 2, H // 2) if op == "CHROMA_SATD" else (W, H)
+        rect(a, px, w, h, sa); rect(b, px, w, h, sb); flat(d, 8, True)
+    elif op in ("SAD_X3", "SAD_X4"):
+        rect(a, px, W, H, FENC_STRIDE)
+        for cand in (b, c, e0, e1)[:3 if op == "SAD_X3" else 4]:
+            rect(cand, px, W, H, sb)
+        flat(d, 4 * (3 if op == "SAD_X3" else 4), True)
+    elif op in ("SA8D", "SSE_PP", "PSY_COST_PP", "CHROMA_SA8D"):
+        n = N // 2 if op == "CHROMA_SA8D" else N
+        rect(a, px, n, n, sa); rect(b, px, n, n, sb); flat(d, 8, True)
+    elif op == "SSE_SS":
+        rect(a, 2, N, N, sa); rect(b, 2, N, N, sb); flat(d, 8, True)
+    elif op == "SSD_S":
+        rect(a, 2, N, N, sa); flat(d, 8, True)
+    elif op == "VAR":
+        rect(a, px, N, N, sa); flat(d, 8, True)
+    elif op == "SUB_PS":
+        rect(a, px, N, N, sa); rect(b, px, N, N, sb); rect(d, 2, N, N, sd, True)
+    elif op == "ADD_PS":
+        rect(a, px, N, N, sa); rect(b, 2, N, N, sb); rect(d, px, N, N, sd, True)
+    elif op == "PIXELAVG_PP":
+        rect(a, px, W, H, sa); rect(b, px, W, H, sb); rect(d, px, W, H, sd, True)
+    elif op == "ADDAVG":
+        w, h = W >> p[0], H >> p[0]
+        rect(a, 2, w, h, sa); rect(b, 2, w, h, sb); rect(d, px, w, h, sd, True)
+    elif op in ("WEIGHT_PP", "WEIGHT_SP"):
+        rect(a, px if op == "WEIGHT_PP" else 2, p[0], p[1], sa); rect(d, px, p[0], p[1], sd, True)
+    elif op == "SCALE2D_64TO32":
+        rect(a, px, 64, 64, sa); flat(d, 32 * 32 * px, True)
+    elif op == "SCALE1D_128TO64":
+        flat(a, 256 * px); flat(d, 128 * px, True)
+    elif op == "TRANSPOSE":
+        rect(a, px, N, N, sa); flat(d, N * N * px, True)
+    elif op in ("CPY2DTO1D_SHL", "CPY2DTO1D_SHR"):
+        rect(a, 2, N, N, sa); flat(d, N * N * 2, True)
+    elif op in ("CPY1DTO2D_SHL", "CPY1DTO2D_SHR"):
+        flat(a, N * N * 2); rect(d, 2, N, N, sd, True)
+    elif op == "COPY_CNT":
+        rect(a, 2, N, N, sa); flat(d, N * N * 2, True); flat(e0, 8, True)
+    elif op == "COUNT_NONZERO":
+        flat(a, N * N * 2); flat(d, 8, True)
+    elif op in ("DCT", "DST4"):
+        n = 4 if op == "DST4" else N
+        rect(a, 2, n, n, sa); flat(d, n * n * 2, True)
+    elif op in ("IDCT", "IDST4"):
+        n = 4 if op == "IDST4" else N
+        flat(a, n * n * 2); rect(d, 2, n, n, sd, True)
+    elif op in ("QUANT", "NQUANT"):
+        num = p[2]
+        flat(a, 2 * num); flat(b, 4 * num); flat(d, 2 * num, True); flat(e1, 8, True)
+        if op == "QUANT":
+            flat(e0, 4 * num, True)
+    elif op in ("DEQUANT_NORMAL", "DEQUANT_SCALING"):
+        num = p[0]
+        flat(a, 2 * num); flat(d, 2 * num, True)
+        if op == "DEQUANT_SCALING":
+            flat(b, 4 * num)
+    elif op in ("INTRA_PRED", "INTRA_FILTER", "INTRA_ALLANGS"):
+        assert 0 <= size < 4        # the kernel's LDS neighbour rows hold 4 * 32 + 1 samples
+        flat(a, (4 * N + 1) * px)
+        if op == "INTRA_PRED":
+            assert 0 <= p[0] < 35
+            rect(d, px, N, N, sd, True)
+        elif op == "INTRA_FILTER":
+            flat(d, (4 * N + 1) * px, True)
+        else:
+            flat(b, (4 * N + 1) * px); flat(d, 33 * N * N * px, True)
+    elif op.startswith("IP_"):
+        taps, w, h, idx, aux = p[:5]
+        assert taps in (4, 8) and 0 <= idx < (4 if taps == 8 else 8) and w > 0 and h > 0
+        half, rest = taps // 2 - 1, taps - 1 - (taps // 2 - 1)
+        horiz = op in ("IP_HPP", "IP_HPS", "IP_HVPP")
+        vert = op in ("IP_VPP", "IP_VPS", "IP_VSP", "IP_VSS", "IP_HVPP") or (op == "IP_HPS" and aux != 0)
+        if op == "IP_HVPP":
+            assert 0 <= aux < 4
+        se, de = (2 if op in ("IP_VSP", "IP_VSS") else px), (2 if op in ("IP_HPS", "IP_VPS", "IP_VSS", "IP_P2S") else px)
+        mx, mxr, mt, mb = (half if horiz else 0), (rest if horiz else 0), (half if vert else 0), (rest if vert else 0)
+        rect(a - (mt * sa + mx) * se, se, w + mx + mxr, h + mt + mb, sa, block_w=w)
+        rect(d, de, w, h + (taps - 1 if op == "IP_HPS" and aux else 0), sd, True)
+    else:
+        raise AssertionError("unknown op %r" % op)
+    return out
+
+
+def job_result_field(op):
+    """(field, alignment) of the op's scalar result, as the layer-2 comment of include/x265amd.h states it: a 64-bit word in d, or in e[0] / e[1] where the op has
+    other use for d; sad_x3 / sad_x4: int32 values in d.  (None, 0): the op has blocks only"""
+    if op in ("SAD_X3", "SAD_X4"):
+        return "d", 4
+    if JOB_OPS[op] // 32 == 0 or op == "COUNT_NONZERO":
+        return "d", 8
+    if op == "COPY_CNT":
+        return "e0", 8
+    if op in ("QUANT", "NQUANT"):
+        return "e1", 8
+    return None, 0
+
+
+def job_assert_inside(recs, specs, depth, in_base, in_size, out_base, out_size):
+    """no record may make a kernel read outside the input arena or write outside its own output region: checked on the host before anything is launched"""
+    for i, (r, s) in enumerate(zip(recs, specs)):
+        assert int(r["op"]) // 32 == int(recs[0]["op"]) // 32, "job %d: one family per launch" % i
+        for lo, hi, write in job_touch(r, depth):
+            base, size = (out_base, out_size) if write else (in_base, in_size)
+            assert base <= lo < hi <= base + size, "job %d (%s): %s range [%d, %d) outside its arena [0, %d)" % (i, s.name(), "write" if write else "read", lo - base, hi - base, size)
+        field, align = job_result_field(JOB_OP_NAME[s.op])
+        if field:
+            addr = int(r["e"][int(field[1])]) if field in ("e0", "e1") else int(r[field])
+            assert addr % align == 0, "job %d (%s): result %s not %d-byte aligned" % (i, s.name(), field, align)
+    writes = sorted((lo, hi, i) for i, r in enumerate(recs) for lo, hi, write in job_touch(r, depth) if write)
+    for (lo0, hi0, i0), (lo1, hi1, i1) in zip(writes, writes[1:]):
+        assert hi0 <= lo1, "jobs %d and %d write overlapping ranges" % (i0, i1)
+
+
+def job_expected(O, arena, specs):
+    """the output arena after the oracle has run the given jobs on the host copies: poison everywhere else"""
+    want = arena.poison()
+    M = _JobHost(arena.inb, want)
+    for s in specs:
+        s.oracle(O, M)
+    return want
+
+
+def job_regions(arena, specs, depth):
+    """[(first byte, one past the last, job index)] of the output arena, sorted: where each job of the batch writes"""
+    recs = job_records(specs, 0, 0)
+    reg = []
+    for i, r in enumerate(recs):
+        # input offsets are taken from base 0 as well, which is harmless here: only the writes are kept
+        reg += [(lo, hi, i) for lo, hi, write in job_touch(r, depth) if write]
+    return sorted(reg)
+
+
+def job_compare(arena, specs, depth, got, want, what):
+    """whole-arena comparison; a mismatch names the job, its op and size index and the first differing position"""
+    if np.array_equal(got, want):
+        return
+    bad = np.flatnonzero(got != want)
+    first = int(bad[0])
+    reg = job_regions(arena, specs, depth)
+    owner = [(lo, hi, i) for lo, hi, i in reg if lo <= first < hi]
+    if owner:
+        lo, hi, i = owner[0]
+        where = "inside the output of job %d (%s), byte %d of its %d" % (i, specs[i].name(), first - lo, hi - lo)
+    else:
+        before = [(lo, hi, i) for lo, hi, i in reg if hi <= first]
+        where = "OUTSIDE every job's output" + (", %d bytes behind that of job %d (%s)" % (first - before[-1][1], before[-1][2], specs[before[-1][2]].name()) if before else "")
+    jobs = sorted({i for lo, hi, i in reg if np.any(got[lo:hi] != want[lo:hi])})
+    raise AssertionError("%s: %d bytes of the output arena differ, the first at offset %d, %s: got 0x%02x want 0x%02x (poison 0x%02x); jobs with differences: %s"
+                         % (what, bad.size, first, where, got[first], want[first], (first * 37 + 11) & 0xFF, jobs[:16]))
+
+
+def job_run_device(L, arena, specs, family, stream=None):
+    """uploads both arenas verbatim, checks every record's reach on the host, launches the batch (stream: None, or a torch.cuda.Stream) and returns the output arena
+    as the device left it"""
+    import torch
+    d_in = torch.from_numpy(arena.inb).cuda()
+    d_out = torch.from_numpy(arena.poison()).cuda()
+    recs = job_records(specs, d_in.data_ptr(), d_out.data_ptr())
+    job_assert_inside(recs, specs, L.depth, d_in.data_ptr(), arena.inb.size, d_out.data_ptr(), arena.out_size)
+    d_jobs = torch.from_numpy(recs.view(np.uint8).copy()).cuda()
+    torch.cuda.synchronize()
+    handle = None if stream is None else C.c_void_p(stream.cuda_stream)
+    assert L.lib.x265amd_run_jobs(handle, C.c_void_p(d_jobs.data_ptr()), len(specs), family) == 0
+    if stream is not None:
+        stream.synchronize()
+    torch.cuda.synchronize()
+    got = d_out.cpu().numpy()
+    assert np.array_equal(d_in.cpu().numpy(), arena.inb), "the input arena changed"
+    return got

@@ -1252,6 +1252,42 @@ void x265amd_hist_scene_state_init(x265amd_hist_scene_state* state);
 int x265amd_hist_scene_change(const x265amd_hist_scene_pic* previous, const x265amd_hist_scene_pic* current, const x265amd_hist_scene_pic* future, int width, int height,
                               x265amd_hist_scene_state* state, int32_t* verdicts);
 
+/* Quality metrics (--psnr, --ssim, measured light levels): picture-wide reductions of the source and the reconstructed picture where both already are, in device
+ * memory; a few words per picture come back (csrc/quality_kernels.hip, csrc/quality_dev.h; the host models: host/quality_model.cpp).  Every pass is asynchronous on
+ * `stream`, zeroes or overwrites its own output (a second launch into the same record gives the same record) and has a host model of the same name + _model that takes
+ * host planes and needs no GPU.  Planes: the address of sample (0,0); sizes in luma samples; width x height is the CODED size (multiples of 8, 16 at least), org_width x
+ * org_height the size before padding.  4:2:0.
+ *
+ * x265amd_picture_ssd = FrameFilter::processPostRow's computeSSD over all CTU rows (reference: source/encoder/framefilter.cpp:667-690, encoder.cpp:1121 ff.): per plane the
+ *   sum of squared differences over org_width columns and ALL `height` rows (the rows come from the padded height there); chroma: half of each.  ssd: 3 words.
+ * x265amd_picture_ssim = the luma SSIM sums of processPostRow / calculateSSIM (framefilter.cpp:692-711, :828-853) per CTU row (band) of 64 lines: the band's float32 sum as its
+ *   bit pattern, added in the reference's order, and its window count.  bands: X265AMD_SSIM_BANDS(height) entries.  work: device memory of X265AMD_SSIM_WORK_BYTES(width,
+ *   height) bytes (one float per group of four windows).  block_sums: 0, or the device address of ((height - 2) >> 2) x ((width - 2) >> 2) x 4 int32 that take every 4x4
+ *   block's s1 (reconstruction), s2 (source), ss, s12 (for tests).
+ * x265amd_luma_level = PicYuv::copyFromPicture's light level loop (source/common/picyuv.cpp:426-439): the largest sample and the sum of the samples of a luma plane over
+ *   org_width x org_height.
+ * x265amd_quality_finish = Encoder::finishFrameStats (encoder.cpp:2978-3010, :3071) on those records: psnr = ssd ? 10 log10(refValue / ssd) : 99.99 with refValue =
+ *   (255 << (depth - 8))^2 x org_width x org_height (a quarter for chroma), psnr = (6 Y + U + V) / 8; ssim = (the bands' floats added to a double in band order) / (the sum
+ *   of the counts), 0 when no window was counted; avgLumaLevel = sum / (width x height) -- the PADDED size, as picyuv.cpp:438 divides.  ssd, bands or level may be NULL: the
+ *   values made of it are then 0. */
+typedef struct x265amd_ssim_band { uint32_t sum_bits; uint32_t cnt; } x265amd_ssim_band;
+typedef struct x265amd_luma_level_record { uint64_t sum; uint32_t max; uint32_t reserved; } x265amd_luma_level_record;
+#define X265AMD_SSIM_BANDS(height) (((height) + 63) >> 6)
+#define X265AMD_SSIM_WORK_BYTES(width, height) ((size_t)((((height) - 2) >> 2) - 1) * (size_t)((((((width) - 2) >> 2) - 1) + 3) / 4) * sizeof(float))
+typedef struct x265amd_quality_values { double psnrY, psnrU, psnrV, psnr, ssim, avgLumaLevel; uint32_t maxLumaLevel; uint32_t ssimCnt; } x265amd_quality_values;
+int x265amd_picture_ssd(void* stream, const uint64_t src[3], const uint64_t rec[3], intptr_t stride, intptr_t cstride, int width, int height, int org_width, int org_height,
+                        uint64_t* d_ssd);
+int x265amd_picture_ssim(void* stream, uint64_t src_luma, uint64_t rec_luma, intptr_t stride, int width, int height, x265amd_ssim_band* d_bands, void* d_work,
+                         uint64_t block_sums);
+int x265amd_luma_level(void* stream, uint64_t luma, intptr_t stride, int org_width, int org_height, x265amd_luma_level_record* d_level);
+int x265amd_picture_ssd_model(const x265amd_pixel* const src[3], const x265amd_pixel* const rec[3], intptr_t stride, intptr_t cstride, int width, int height, int org_width,
+                              int org_height, uint64_t* ssd);
+int x265amd_picture_ssim_model(const x265amd_pixel* src_luma, const x265amd_pixel* rec_luma, intptr_t stride, int width, int height, x265amd_ssim_band* bands,
+                               int32_t* block_sums);
+int x265amd_luma_level_model(const x265amd_pixel* luma, intptr_t stride, int org_width, int org_height, x265amd_luma_level_record* level);
+int x265amd_quality_finish(const uint64_t* ssd, const x265amd_ssim_band* bands, const x265amd_luma_level_record* level, int width, int height, int org_width, int org_height,
+                           x265amd_quality_values* out);
+
 /* returns the device scratch the host orchestrators keep between calls (a size-class pool) to the HIP runtime */
 void x265amd_release_scratch(void);
 /* X265AMD_HOSTPROF=1: prints (stderr) the host CPU time by named scope collected so far (development aid) */

@@ -131,17 +131,23 @@ typedef struct x265amd_param
     int32_t vuiColorDescriptionPresent, vuiColorPrimaries, vuiTransfer, vuiMatrix;   /* 2 = unspecified */
     int32_t vuiChromaLocPresent, vuiChromaLocTop, vuiChromaLocBottom;
     int32_t vuiDisplayWindow, vuiDispWinLeft, vuiDispWinRight, vuiDispWinTop, vuiDispWinBottom;
-    int32_t reserved3;
+    int32_t bEnablePsnr;                    /* param.bEnablePsnr (--psnr; 0): every picture's sums of squared differences between source and reconstruction (x265amd_picture_ssd, measured on the
+                                             * device when the picture's last row is final), PSNR per picture (x265amd_encoder_quality) and the sums of x265_stats (x265amd_encoder_stats).
+                                             * Nothing else reads it: the stream is the one coded without it.  Not with shardCount > 1.
+                                             * (The slot was a reserved int32 until the metrics were built: same offset, same four bytes) */
     /* units around the slices (signalling only) */
     int32_t bEnableAccessUnitDelimiters;    /* param.bEnableAccessUnitDelimiters (--aud): an access unit delimiter in front of every picture but the first -- of every picture with
                                              * bRepeatHeaders (frameencoder.cpp:497-506) */
     int32_t bEmitHDR10SEI, bEmitCLL;        /* param.bEmitHDR10SEI (--hdr10; x265_check_params switches it on with any of the values below), param.bEmitCLL (--cll, the default):
                                              * the content light level and mastering display colour volume SEI units behind the parameter sets (encoder.cpp:3264-3282) */
-    int32_t maxCLL, maxFALL;                /* --max-cll "cll,fall" */
+    int32_t maxCLL, maxFALL;                /* --max-cll "cll,fall".  With either set every source picture's light level is measured where it arrives in device memory
+                                             * (x265amd_luma_level; PicYuv::copyFromPicture, picyuv.cpp:426-439) and x265amd_encoder_stats reports the largest sample and the sum of the
+                                             * pictures' averages -- x265_stats.maxCLL / maxFALL.  With shardCount > 1 the levels are not measured and stay 0 */
     int32_t hasMasteringDisplay;            /* --master-display "G(x,y)B(x,y)R(x,y)WP(x,y)L(max,min)": the ten numbers below */
     uint32_t masteringDisplay[10];
     int32_t decodedPictureHashSEI;          /* param.decodedPictureHashSEI (--hash): 0 none, 1 MD5, 2 CRC, 3 checksum of each reconstructed picture in a suffix SEI unit */
-    int32_t reserved4;
+    int32_t bEnableSsim;                    /* param.bEnableSsim (--ssim; 0): the luma SSIM of every picture (x265amd_picture_ssim), as bEnablePsnr.  Not with shardCount > 1.
+                                             * (A reserved int32 before: same offset, same four bytes) */
     int32_t deblockingFilterTCOffset, deblockingFilterBetaOffset;      /* param.deblockingFilter*Offset (--deblock tc:beta, each -6 .. 6): pps_tc_offset_div2 / pps_beta_offset_div2 */
     int32_t limitTU;                        /* param.limitTU (--limit-tu; --preset slower has 4): 0, 2 (depth first), 3 (neighbourhood), 4 (both); 1 (breadth first) is not built.
                                              * Needs tuQTMaxInterDepth > 1 (else it is switched off, encoder.cpp:4103-4107) */
@@ -209,8 +215,27 @@ int x265amd_encoder_owns(const x265amd_encoder* enc, uint64_t coding_index);
 /* counters of the pictures handed over by the lookahead so far (the counterpart of what x265_encoder_get_stats totals, x265.h:2475): out[0] I, out[1] P, out[2] B pictures,
  * out[3] the sum over them of the DISTINCT reference pictures each reads (DPB::prepareEncode's lists, dpb.cpp:101-290) -- SURVEY section 8d's R per picture, which the
  * bench's roofline figure is built from.  With n >= 13 also, of the pictures HANDED OUT so far by I / P / B: out[4..6] their number, out[7..9] the bits of their NAL units,
- * out[10..12] the sums of their average QPs (IEEE doubles, bit for bit in the words) -- x265_stats' statsI / statsP / statsB.  n: words available (>= 4).  Returns 0 or -1. */
+ * out[10..12] the sums of their average QPs (IEEE doubles, bit for bit in the words) -- x265_stats' statsI / statsP / statsB.  n: words available (>= 4).  Returns 0 or -1.
+ * With n >= 31 also what Encoder::finishFrameStats adds up of the quality metrics (encoder.cpp:2999-3043), IEEE doubles bit for bit in the words, in hand-out order:
+ * out[13..16] the sums of the pictures' PSNR Y / U / V and of their SSIM over all pictures, out[17..20] over the I, out[21..24] the P, out[25..28] the B pictures
+ * (zero unless bEnablePsnr / bEnableSsim), out[29] the largest luma sample of any source picture (an integer) and out[30] the sum of the pictures' average luma levels
+ * (zero unless maxCLL or maxFALL is set).  A caller with n < 31 sees none of them. */
 int x265amd_encoder_stats(const x265amd_encoder* enc, uint64_t* out, int n);
+/* The quality record of the picture most recently handed out by x265amd_encoder_encode / _encode_device, and the values Encoder::finishFrameStats makes of it
+ * (x265amd_quality_finish, include/x265amd.h).  measured: bit 0 PSNR (ssd, psnr*), bit 1 SSIM (ssimSum: the bands' float sums added to a double in band order; ssimCnt; ssim),
+ * bit 2 the light level (lumaSum, maxLumaLevel, avgLumaLevel); what was not measured is 0.  Returns 0, or -1 when nothing was measured for that picture (every switch off) or
+ * no picture has been handed out yet. */
+typedef struct x265amd_quality
+{
+    uint64_t ssd[3];
+    double ssimSum;
+    uint64_t lumaSum;
+    uint32_t ssimCnt, maxLumaLevel;
+    double psnrY, psnrU, psnrV, psnr, ssim, avgLumaLevel;
+    int32_t poc, sliceType;
+    int32_t measured, reserved;
+} x265amd_quality;
+int x265amd_encoder_quality(const x265amd_encoder* enc, x265amd_quality* out);
 /* whether pictures coded later may reference picture `coding_index` (DPB::prepareEncode: every picture but a plain B picture; reference: source/encoder/dpb.cpp:101-140):
  * 1 yes, 0 no -- its rows need not travel and an object that does not code it does not wait for them --, 2 not known yet (not handed over by the lookahead: ask again),
  * -1 on error.  The same answer on every object of a set. */

@@ -8,7 +8,7 @@
  *             --crf F --qp N --aq-mode N --aq-strength F --[no-]cutree --qcomp F --qg-size N --bframes N --b-adapt N --[no-]b-pyramid --[no-]open-gop --keyint N --min-keyint N
  *             --scenecut N --no-scenecut --[no-]hist-scenecut --rc-lookahead N --lookahead-slices N --ref N --limit-refs N --rd N --rdoq-level N --psy-rd F --psy-rdoq F --me name --subme N
  *             --merange N --max-merge N --[no-]rect --[no-]amp --[no-]limit-modes --[no-]early-skip --rskip N (0, 1, 2) --rskip-edge-threshold N --[no-]weightp --[no-]weightb --[no-]sao --[no-]deblock --[no-]wpp
- *             --tu-intra-depth N --tu-inter-depth N --[no-]signhide --[no-]strong-intra-smoothing --[no-]temporal-mvp --[no-]b-intra --[no-]fast-intra --[no-]info
+ *             --tu-intra-depth N --tu-inter-depth N --[no-]signhide --[no-]strong-intra-smoothing --[no-]temporal-mvp --[no-]b-intra --[no-]fast-intra --[no-]info --[no-]psnr --[no-]ssim --max-cll C,F
  *             --frame-threads N --pools S ...]
  *
  * Input: YUV4MPEG2, 4:2:0, 8 or 10 bits (source/input/y4m.cpp:150-330 header, :405-441 frames).  Output: the Annex-B stream (source/output/raw.cpp); the reconstruction in
@@ -50,6 +50,7 @@ struct Api
     int encoder_headers(void* e, Nal** nal, uint32_t* n) const { return ((int (*)(void*, Nal**, uint32_t*))t->fn[X265API_ENCODER_HEADERS])(e, nal, n); }
     int encoder_encode(void* e, Nal** nal, uint32_t* n, void* in, void* out) const { return ((int (*)(void*, Nal**, uint32_t*, void*, void*))t->fn[X265API_ENCODER_ENCODE])(e, nal, n, in, out); }
     void encoder_get_stats(void* e, void* stats, uint32_t bytes) const { ((void (*)(void*, void*, uint32_t))t->fn[X265API_ENCODER_GET_STATS])(e, stats, bytes); }
+    void encoder_log(void* e, int argc, char** argv) const { ((void (*)(void*, int, char**))t->fn[X265API_ENCODER_LOG])(e, argc, argv); }
     void encoder_close(void* e) const { ((void (*)(void*))t->fn[X265API_ENCODER_CLOSE])(e); }
     void cleanup() const { ((void (*)(void))t->fn[X265API_CLEANUP])(); }
     FILE* csvlog_open(const void* p) const { return ((FILE* (*)(const void*))t->fn2[4])(p); }
@@ -242,6 +243,8 @@ int main(int argc, char** argv)
             fclose(f);
         }
     }
+    /* the reference's program: x265_encoder_log -> the summary lines of the quality metrics, when one is on (abrEncApp.cpp) */
+    if (rc >= 0) api.encoder_log(enc, argc, argv);
     api.encoder_close(enc);
     api.picture_free(picIn); api.picture_free(picOut);
     api.param_free(p);

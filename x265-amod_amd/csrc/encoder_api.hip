@@ -149,6 +149,9 @@ extern "C" x265amd_encoder* x265amd_encoder_open(const x265amd_param* p)
         /* histogram scene-cut detection: the reference indexes its 256 bins with 10-bit samples (the planes' bins overlap inside its allocation), which is not restated */
         XA_REQUIRE(!p->bHistBasedSceneCut || X265AMD_DEPTH == 8, "bHistBasedSceneCut: histogram scene-cut detection is built for the 8-bit library only");
         XA_REQUIRE(!p->bHistBasedSceneCut || p->shardCount <= 1, "bHistBasedSceneCut with pictures coded on several GPUs (shardCount > 1) is not built");
+        /* the quality metrics are measured by the object that codes a picture and summed by the one that hands it out: no test runs several ranks */
+        XA_REQUIRE(!p->bEnablePsnr || p->shardCount <= 1, "bEnablePsnr with pictures coded on several GPUs (shardCount > 1) is not built");
+        XA_REQUIRE(!p->bEnableSsim || p->shardCount <= 1, "bEnableSsim with pictures coded on several GPUs (shardCount > 1) is not built");
         XA_REQUIRE(p->limitReferences >= 0 && p->limitReferences <= 3, "limitReferences outside 0..3");
         XA_REQUIRE(!p->bEnableAMP || p->bEnableRectInter, "bEnableAMP needs bEnableRectInter");
 #undef XA_REQUIRE
@@ -187,6 +190,7 @@ extern "C" x265amd_encoder* x265amd_encoder_open(const x265amd_param* p)
     if (p->bFrameAdaptive < 0 || p->bFrameAdaptive > 2) { xa_fail(X265AMD_EINVAL, "encoder_open: bFrameAdaptive: 0 (fixed mini-GOPs), 1 (fast) or 2 (trellis)"); return nullptr; }
     e->lookahead = p->scenecutThreshold > 0 || p->bHistBasedSceneCut || (p->bFrameAdaptive && p->bframes) || p->cuTree || p->aqMode;          /* (slicetype.cpp:1909-1912) */
     x265amd_hist_scene_state_init(&e->histState);
+    if (e->measuresLevel() && xa_scratch_alloc((void**)&e->levelDev, sizeof(x265amd_luma_level_record)) != hipSuccess) { xa_fail(X265AMD_EHIP, "encoder_open: light level record"); return nullptr; }
     if ((p->bEnableWeightedPred || p->bEnableWeightedBiPred) && !e->lookahead) { xa_fail(X265AMD_EINVAL, "encoder_open: bEnableWeightedPred needs the lookahead (scenecutThreshold > 0 or bFrameAdaptive 2 with B frames)"); return nullptr; }
     {
         /* Encoder::configure (encoder.cpp:3658-3663) */
@@ -350,6 +354,34 @@ extern "C" int x265amd_encoder_stats(const x265amd_encoder* e, uint64_t* out, in
     out[0] = e->statPictures[0]; out[1] = e->statPictures[1]; out[2] = e->statPictures[2]; out[3] = e->statReferences;
     if (n >= 13)
         for (int t = 0; t < 3; t++) { out[4 + t] = e->statEmitted[t]; out[7 + t] = e->statBits[t]; memcpy(&out[10 + t], &e->statQpSum[t], 8); }
+    if (n >= 31)
+    {
+        for (int g = 0; g < 4; g++)
+        {
+            for (int k = 0; k < 3; k++) memcpy(&out[13 + 4 * g + k], &e->statPsnr[g][k], 8);
+            memcpy(&out[13 + 4 * g + 3], &e->statSsim[g], 8);
+        }
+        out[29] = e->statMaxCll;
+        memcpy(&out[30], &e->statFallSum, 8);
+    }
+    return 0;
+}
+extern "C" int x265amd_encoder_quality(const x265amd_encoder* e, x265amd_quality* out)
+{
+    if (!e || !out) return xa_fail(X265AMD_EINVAL, "encoder_quality: arguments"), -1;
+    if (!e->haveQuality || !e->lastQuality.measured) return -1;
+    *out = e->lastQuality;
+    return 0;
+}
+/* PicYuv::copyFromPicture's light level loop (picyuv.cpp:426-439) where the source picture has just arrived in device memory: one pass on the stream the upload ran on */
+int x265amd_encoder::measureLevel(Pic& pic)
+{
+    x265amd_luma_level_record level;
+    if (x265amd_luma_level(nullptr, planeAddr(pic.dSrc, 0), stride, srcW, srcH, levelDev) != X265AMD_OK) return -1;
+    if (hipMemcpy(&level, levelDev, sizeof(level), hipMemcpyDeviceToHost) != hipSuccess) return xa_fail(X265AMD_EHIP, "encoder_encode: light level");
+    x265amd_quality_values v;
+    if (x265amd_quality_finish(nullptr, nullptr, &level, W, H, srcW, srcH, &v) != X265AMD_OK) return xa_fail(X265AMD_EINVAL, "encoder_encode: light level");
+    pic.quality.lumaSum = level.sum; pic.quality.maxLumaLevel = level.max; pic.quality.avgLumaLevel = v.avgLumaLevel; pic.quality.measured |= 4;
     return 0;
 }
 extern "C" int x265amd_encoder_row_geometry(const x265amd_encoder* e, int row, x265amd_row_export* out)
@@ -568,6 +600,7 @@ static int encoder_encode_impl(x265amd_encoder* e, x265amd_nal** ppNal, uint32_t
         const auto tu0 = std::chrono::steady_clock::now();
         int rc = e->uploadPicture(picIn, *pic, inputOnDevice);
         if (rc) return -1;
+        if (e->measuresLevel() && e->measureLevel(*pic)) return -1;
         const auto tl0 = std::chrono::steady_clock::now();
         e->uploadMs += std::chrono::duration<double, std::milli>(tl0 - tu0).count();
         if (e->lookahead && (rc = e->lowresInit(*pic)) != X265AMD_OK) return -1;
@@ -779,6 +812,19 @@ static int encoder_encode_impl(x265amd_encoder* e, x265amd_nal** ppNal, uint32_t
         if (e->useDqp && front->units.size() >= n) { int64_t sum = 0; for (size_t i = 0; i < n; i++) sum += front->units[i].qp; q = (double)sum / (double)n; }
         else q = front->sliceQp;
         e->statEmitted[t]++; e->statBits[t] += (uint64_t)e->outBytes.size() * 8; e->statQpSum[t] += q;
+        if (front->quality.measured)
+        {
+            /* EncStats::addPsnr / addSsim over all pictures and the picture's type, the light levels (encoder.cpp:2999-3043) */
+            const x265amd_quality& m = front->quality;
+            for (int g : { 0, 1 + t })
+            {
+                if (m.measured & 1) { e->statPsnr[g][0] += m.psnrY; e->statPsnr[g][1] += m.psnrU; e->statPsnr[g][2] += m.psnrV; }
+                if ((m.measured & 2) && m.ssimCnt) e->statSsim[g] += m.ssim;
+            }
+            if (m.measured & 4) { e->statFallSum += m.avgLumaLevel; e->statMaxCll = std::max(e->statMaxCll, m.maxLumaLevel); }
+            e->lastQuality = m; e->lastQuality.poc = front->poc; e->lastQuality.sliceType = front->type;
+        }
+        e->haveQuality = front->quality.measured != 0;
     }
     if (picOut)
     {

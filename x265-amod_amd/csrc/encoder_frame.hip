@@ -158,6 +158,51 @@ int x265amd_encoder::edgeCounts(Pic& pic, hipStream_t st, x265amd_rskip_edge& ed
     return X265AMD_OK;
 }
 
+/* --psnr / --ssim: what FrameFilter::processPostRow measures row by row after SAO (framefilter.cpp:667-711), as picture-wide passes over the source and the FINAL
+ * reconstruction, both in device memory, once the picture's last row is final; a few words come back (x265amd_picture_ssd / _ssim, csrc/quality_kernels.hip) and
+ * Encoder::finishFrameStats' values are made of them (x265amd_quality_finish).  On the picture's own stream, waited for here: the picture is handed out after its task. */
+int x265amd_encoder::measureQuality(Pic& pic, hipStream_t st)
+{
+    if (!pic.dSrc) return xa_fail(X265AMD_EINVAL, "encoder: the picture's source is gone");
+    const pixel* fin = pic.finalPlanes();
+    const int nb = X265AMD_SSIM_BANDS(H);
+    const size_t ssdBytes = 3 * sizeof(uint64_t), bandBytes = (size_t)nb * sizeof(x265amd_ssim_band), workBytes = X265AMD_SSIM_WORK_BYTES(W, H);
+    struct Scratch { void* p = nullptr; ~Scratch() { xa_scratch_free(p); } } dev;
+    if (xa_scratch_alloc(&dev.p, ssdBytes + bandBytes + workBytes) != hipSuccess) return xa_fail(X265AMD_EHIP, "encoder: quality record");
+    uint64_t* dSsd = (uint64_t*)dev.p;
+    x265amd_ssim_band* dBands = (x265amd_ssim_band*)((char*)dev.p + ssdBytes);
+    std::vector<uint64_t> host((ssdBytes + bandBytes) / sizeof(uint64_t), 0);
+    if (p.bEnablePsnr)
+    {
+        const uint64_t srcP[3] = { planeAddr(pic.dSrc, 0), planeAddr(pic.dSrc, 1), planeAddr(pic.dSrc, 2) };
+        const uint64_t recP[3] = { planeAddr(fin, 0), planeAddr(fin, 1), planeAddr(fin, 2) };
+        const int rc = x265amd_picture_ssd(st, srcP, recP, stride, cstride, W, H, srcW, srcH, dSsd);
+        if (rc != X265AMD_OK) return rc;
+    }
+    if (p.bEnableSsim)
+    {
+        const int rc = x265amd_picture_ssim(st, planeAddr(pic.dSrc, 0), planeAddr(fin, 0), stride, W, H, dBands, (char*)dev.p + ssdBytes + bandBytes, 0);
+        if (rc != X265AMD_OK) return rc;
+    }
+    /* (what a switch that is off leaves unwritten is not read below) */
+    if (hipMemcpyAsync(host.data(), dev.p, ssdBytes + bandBytes, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+        return xa_fail(X265AMD_EHIP, "encoder: quality passes");
+    const uint64_t* ssd = p.bEnablePsnr ? host.data() : nullptr;
+    const x265amd_ssim_band* bands = p.bEnableSsim ? (const x265amd_ssim_band*)(host.data() + 3) : nullptr;
+    x265amd_quality_values v;
+    const int rc = x265amd_quality_finish(ssd, bands, nullptr, W, H, srcW, srcH, &v);
+    if (rc != X265AMD_OK) return xa_fail(rc, "encoder: quality values");
+    x265amd_quality& q = pic.quality;
+    if (ssd) { for (int k = 0; k < 3; k++) q.ssd[k] = ssd[k]; q.psnrY = v.psnrY; q.psnrU = v.psnrU; q.psnrV = v.psnrV; q.psnr = v.psnr; q.measured |= 1; }
+    if (bands)
+    {
+        double sum = 0.0;       /* FrameEncoder::m_ssim: a double that takes every band's float (framefilter.cpp:708) */
+        for (int r = 0; r < nb; r++) { float f; memcpy(&f, &bands[r].sum_bits, sizeof(float)); sum += f; }
+        q.ssimSum = sum; q.ssimCnt = v.ssimCnt; q.ssim = v.ssim; q.measured |= 2;
+    }
+    return X265AMD_OK;
+}
+
 /* FrameEncoder::compressFrame for one picture (its own thread and HIP stream).  The analysis starts when every reference picture is final; the
  * in-loop filters, SAO (its decision carries state from picture to picture, SAO::m_depthSaoRate) and the shared filter scratch run in coding
  * order, i.e. after the previous picture's task. */
@@ -272,6 +317,7 @@ int x265amd_encoder::runFrame(const PicP& picp, std::shared_future<int> prev)
     if (rc == X265AMD_OK) rc = x265amd_extend_pic_border(st, recV, cstride, W / 2, H / 2, marginX / 2, marginY / 2);
     if (rc != X265AMD_OK) return rc;
     if (hipStreamSynchronize(st) != hipSuccess) return xa_fail(X265AMD_EHIP, "encoder: border extension");
+    if (p.bEnablePsnr || p.bEnableSsim) { rc = measureQuality(pic, st); if (rc != X265AMD_OK) return rc; }
 
     rc = sliceNal(*this, pic, fc, saoFlags, data, sizes, nsub);
     if (rc) return rc;
@@ -773,6 +819,8 @@ int x265amd_encoder::runFrameParallel(const PicP& picp)
     filters.join();
     if (arc != X265AMD_OK) return rc = arc;
     if (filterRc != X265AMD_OK) return rc = filterRc;
+    /* every row is final (the filter thread's last publication; it runs with both filters off, too) and the source is still there */
+    if (p.bEnablePsnr || p.bEnableSsim) { arc = measureQuality(pic, st); if (arc != X265AMD_OK) return rc = arc; }
     if (sao)
     {
         arc = x265amd_encode_slice_data(&fc.si, pic.units.data(), coeff.data(), sparams.data(), saoFlags, data.data(), data.size(), sizes.data(), &nsub);

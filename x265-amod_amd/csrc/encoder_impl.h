@@ -124,6 +124,7 @@ struct Pic
     std::vector<int8_t> tuRecs;         /* --limit-tu 3 / 4: CUData::m_refTuDepth of every CTU (XaTuRecs) */
     std::unique_ptr<x265amd_hist_scene_pic> hist;          /* --hist-scenecut: what LookaheadTLD::collectPictureStatistics leaves in Lowres (x265amd_hist_scene_finish; lowresInit) */
     bool bHistScenecutAnalyzed = false;                    /* Lowres::bHistScenecutAnalyzed */
+    x265amd_quality quality;            /* --psnr / --ssim / measured light levels: the picture's record (x265amd_encoder::measureLevel at upload, measureQuality when its last row is final) */
     uint32_t* edgeCounts = nullptr;     /* --rskip 2, P / B pictures: Frame::m_edgeBitPic as the ones of every 32x32 block (mapped host memory the device pass writes; x265amd_encoder::edgeCounts) */
     /* ---- rate control other than constant QP (round 6): what adaptive quantisation and cuTree keep of a picture's Lowres (common/lowres.h) ---- */
     std::vector<int32_t> intraCostHost;                     /* Lowres::intraCost per lowres block (read back once, in lowresInit) */
@@ -147,7 +148,7 @@ struct Pic
         regMotion = motion.data();
         if (!xa_devmap_register(regMotion, motion.size())) regMotion = nullptr;
     }
-    Pic() { memset(refPoc, 0, sizeof(refPoc)); memset(wp, 0, sizeof(wp)); for (int i = 0; i < 18; i++) { costEst[i] = -1; intraMbs[i] = 0; specIntraMbs[i] = 0; for (int j = 0; j < 18; j++) cost2[i][j] = specCost2[i][j] = -1; } }
+    Pic() { memset(refPoc, 0, sizeof(refPoc)); memset(wp, 0, sizeof(wp)); memset(&quality, 0, sizeof(quality)); for (int i = 0; i < 18; i++) { costEst[i] = -1; intraMbs[i] = 0; specIntraMbs[i] = 0; for (int j = 0; j < 18; j++) cost2[i][j] = specCost2[i][j] = -1; } }
     ~Pic() { if (pool) { for (auto& e : dLc) pool->put(e.second); for (auto& e : dSpecLc) pool->put(e.second);
                          for (int i = 0; i < 18; i++) for (const std::vector<int16_t>* v : { &lowMvs[i], &lowMvs1[i], &specMvs[i], &specMvs1[i] }) if (!v->empty()) pool->dead(v->data()); } if (regMotion) xa_devmap_unregister(regMotion); xa_scratch_free(dSrc); xa_scratch_free(dRec); xa_scratch_free(dFin); xa_scratch_free(dLowres); xa_scratch_free(dIntraCost); if (edgeCounts) xa_mapped_free(edgeCounts); for (volatile uint64_t* c : finalX) xa_counter_free(c); }
     void publish(int row, int x)
@@ -197,6 +198,15 @@ struct x265amd_encoder
     uint64_t collectedCoding = 0;                       /* pictures collected so far (under byCodingMu) */
     uint64_t statPictures[3] = { 0, 0, 0 }, statReferences = 0;     /* x265amd_encoder_stats: pictures prepared as I / P / B, the sum of their distinct reference pictures */
     uint64_t statEmitted[3] = { 0, 0, 0 }, statBits[3] = { 0, 0, 0 }; double statQpSum[3] = { 0, 0, 0 };       /* ... and of the pictures handed out: count, NAL bits, the sum of their average QPs, by I / P / B */
+    /* quality metrics (param.bEnablePsnr / bEnableSsim; light levels with maxCLL || maxFALL): EncStats' sums of Encoder::finishFrameStats (encoder.cpp:2999-3043) over all
+     * pictures handed out [0] and by I / P / B [1..3], the record of the last picture handed out, the device record of the light level pass (the encoder's: uploads are serial) */
+    double statPsnr[4][3] = { { 0, 0, 0 }, { 0, 0, 0 }, { 0, 0, 0 }, { 0, 0, 0 } }, statSsim[4] = { 0, 0, 0, 0 }, statFallSum = 0;
+    uint32_t statMaxCll = 0;
+    x265amd_quality lastQuality = {}; bool haveQuality = false;
+    x265amd_luma_level_record* levelDev = nullptr;
+    bool measuresLevel() const { return (p.maxCLL || p.maxFALL) && p.shardCount <= 1; }
+    int measureLevel(Pic& pic);                         /* after the upload, on the stream the upload ran on */
+    int measureQuality(Pic& pic, hipStream_t st);       /* the picture's last row is final: its passes on its own stream, waited for */
     std::shared_future<int> lastTask;                   /* the previous picture's task: in-loop filters and SAO run in coding order */
     int frameThreads = 1;
     double uploadMs = 0;        /* X265AMD_TIMING: the callers' time in uploadPicture */
@@ -232,6 +242,7 @@ struct x265amd_encoder
         if (dDbUnits) (void)hipFree(dDbUnits);
         xa_scratch_free(dSaoTmp);
         xa_scratch_free(histRecord);
+        xa_scratch_free(levelDev);
         if (histRecordHost) xa_mapped_free(histRecordHost);
         if (laStream) (void)hipStreamDestroy(laStream);
         if (importStream) (void)hipStreamDestroy(importStream);

@@ -7,7 +7,7 @@
  * reference's header (numbers only) and tests/layout_check.cpp pins against it again; the reference's header itself is not part of this build.
  *
  * Built entries: param_alloc / param_free, picture_alloc / picture_free / picture_init, encoder_open, encoder_parameters, encoder_headers, encoder_encode,
- * encoder_get_stats (zeroes), encoder_log (no-op), encoder_close, cleanup.  Entries of features outside the built subset FAIL CLEANLY: param_default fills the
+ * encoder_get_stats (with --psnr / --ssim / --max-cll the measured values), encoder_log (the summary lines when a metric is on), encoder_close, cleanup.  Entries of features outside the built subset FAIL CLEANLY: param_default fills the
  * reference's defaults for the members encoder_open reads and zeroes the rest, param_default_preset accepts NULL / "medium" only (the other presets' option
  * tables are not restated), param_parse / zone_param_parse / scenecut_aware_qp_param_parse report a bad name, encoder_reconfig* / intra_refresh / ctu_info /
  * get_slicetype_poc_and_scenecut / get_ref_frame_list / set_analysis_data return -1, csvlog_open returns NULL.  encoder_open rejects every parameter outside the
@@ -22,6 +22,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <limits.h>
+#include <math.h>
 #include <string.h>
 #include <time.h>
 #include <vector>
@@ -49,6 +50,7 @@ struct AbiEncoder
     uint64_t coded = 0;                 /* pictures handed out so far */
     double fps = 25.0;
     struct timespec opened = { 0, 0 };   /* x265_stats.elapsedEncodeTime counts from encoder_open */
+    bool psnr = false, ssim = false, levels = false;    /* what Encoder::configure left of bEnablePsnr / bEnableSsim; maxCLL || maxFALL (fetchStats, encoder.cpp:2962) */
     std::vector<uint8_t> recon;         /* the reconstruction handed out by the last encoder_encode: valid until the next call on this encoder (the reference hands out its own picture) */
 };
 
@@ -196,7 +198,8 @@ int abi_param_parse(void* p, const char* name, const char* value)
         { "b-intra", X265ABI_PARAM_bIntraInBFrames }, { "limit-modes", X265ABI_PARAM_limitModes }, { "cutree", X265ABI_PARAM_rc_cuTree }, { "info", X265ABI_PARAM_bEmitInfoSEI },
         { "annexb", X265ABI_PARAM_bAnnexB }, { "repeat-headers", X265ABI_PARAM_bRepeatHeaders }, { "aud", X265ABI_PARAM_bEnableAccessUnitDelimiters }, { "hdr10", X265ABI_PARAM_bEmitHDR10SEI },
         { "hdr", X265ABI_PARAM_bEmitHDR10SEI }, { "cll", X265ABI_PARAM_bEmitCLL }, { "tskip", X265ABI_PARAM_bEnableTransformSkip }, { "lossless", X265ABI_PARAM_bLossless },
-        { "hist-scenecut", X265ABI_PARAM_bHistBasedSceneCut } };          /* (param.cpp:1279) */
+        { "hist-scenecut", X265ABI_PARAM_bHistBasedSceneCut },            /* (param.cpp:1279) */
+        { "psnr", X265ABI_PARAM_bEnablePsnr }, { "ssim", X265ABI_PARAM_bEnableSsim } };
     if (!strcmp(key, "deblock") && !neg && value)
     {
         /* --deblock tc:beta | tc,beta | tc | a truth value (param.cpp:1083-1097) */
@@ -218,7 +221,7 @@ int abi_param_parse(void* p, const char* name, const char* value)
         { "tu-inter-depth", X265ABI_PARAM_tuQTMaxInterDepth }, { "limit-tu", X265ABI_PARAM_limitTU }, { "rskip", X265ABI_PARAM_recursionSkipMode }, { "aq-mode", X265ABI_PARAM_rc_aqMode },
         { "qg-size", X265ABI_PARAM_rc_qgSize }, { "ctu", X265ABI_PARAM_maxCUSize }, { "min-cu-size", X265ABI_PARAM_minCUSize }, { "max-tu-size", X265ABI_PARAM_maxTUSize },
         { "slices", X265ABI_PARAM_maxSlices }, { "level-idc", X265ABI_PARAM_levelIdc }, { "log-level", X265ABI_PARAM_logLevel }, { "qpmin", X265ABI_PARAM_rc_qpMin }, { "qpmax", X265ABI_PARAM_rc_qpMax },
-        { "qpstep", X265ABI_PARAM_rc_qpStep }, { "vbv-bufsize", X265ABI_PARAM_rc_vbvBufferSize }, { "vbv-maxrate", X265ABI_PARAM_rc_vbvMaxBitrate } };
+        { "qpstep", X265ABI_PARAM_rc_qpStep }, { "csv-log-level", X265ABI_PARAM_csvLogLevel }, { "vbv-bufsize", X265ABI_PARAM_rc_vbvBufferSize }, { "vbv-maxrate", X265ABI_PARAM_rc_vbvMaxBitrate } };
     for (const auto& it : ints)
         if (!strcmp(key, it.name)) { const int v = num(bad); wr<int32_t>(p, it.off, v); return bad ? -2 : 0; }          /* (the reference stores what atoi made of a bad value, too) */
     static const struct { const char* name; size_t off; } reals[] = {
@@ -442,6 +445,10 @@ void* abi_encoder_open(void* p)
     q.vuiDispWinTop = PI(p, vui_defDispWinTopOffset); q.vuiDispWinBottom = PI(p, vui_defDispWinBottomOffset);
     q.psyRdoqFix8 = q.rdoqLevel ? (int32_t)(PD(p, psyRdoq) * 256.0) : 0;         /* Quant::init: m_psyRdoqScale = (int32_t)(psyScale * 256.0) (quant.cpp:188) */
     q.bEnableFastIntra = PI(p, bEnableFastIntra);
+    /* Encoder::configure (encoder.cpp:3950-3955): below the info level nobody would see the numbers, and they are not measured.  (The warnings about psy-rd and AQ under the
+     * metrics, :3957-3977, are text; nothing else reads the switches: the stream is the one coded without them) */
+    const bool logInfo = PI(p, logLevel) >= 2 /* X265_LOG_INFO */;
+    q.bEnablePsnr = logInfo && PI(p, bEnablePsnr) != 0; q.bEnableSsim = logInfo && PI(p, bEnableSsim) != 0;
     /* frame threads: 0 = by core count, which is more than one on any machine with four cores or more (threadpool.cpp:661-677); the stream of the
      * frame-parallel rules does not depend on the number */
     /* Encoder::create (encoder.cpp:199-254): no wavefronts in a picture of one CTU row or fewer than three CTU columns ("pointless and unstable") -- and without wavefronts the
@@ -457,6 +464,8 @@ void* abi_encoder_open(void* p)
     a->enc = e; a->width = q.sourceWidth; a->height = q.sourceHeight;
     a->bframeDelay = q.bframes ? (q.bBPyramid ? 2 : 1) : 0;
     a->param.assign((const uint8_t*)p, (const uint8_t*)p + X265ABI_SIZEOF_PARAM);         /* api.cpp:96-116: the encoder keeps a copy */
+    a->psnr = q.bEnablePsnr != 0; a->ssim = q.bEnableSsim != 0; a->levels = q.maxCLL || q.maxFALL;
+    wr<int32_t>(a->param.data(), X265ABI_PARAM_bEnablePsnr, q.bEnablePsnr); wr<int32_t>(a->param.data(), X265ABI_PARAM_bEnableSsim, q.bEnableSsim);
     if ((q.keyframeMax >= 0 && q.keyframeMax <= 1) || q.bEmitHDR10SEI) wr<int32_t>(a->param.data(), X265ABI_PARAM_bRepeatHeaders, 1);          /* ... as Encoder::configure left it: x265_encoder_parameters tells the caller (the reference's program asks before it writes the headers) */
     a->fps = (double)q.fpsNum / (double)q.fpsDenom;
     clock_gettime(CLOCK_MONOTONIC, &a->opened);
@@ -523,8 +532,21 @@ int abi_encoder_encode(void* enc, x265amd_nal** ppNal, uint32_t* piNal, void* pi
     }
     return ret;
 }
-/* x265_encoder_get_stats (Encoder::fetchStats, encoder.cpp:2870-2960): what this encoder counts -- pictures, bits and average QP by slice type, the times and the bit rate.
- * PSNR / SSIM (off unless asked for, and then not built), the light levels and the weighted-frame count stay 0. */
+/* x265_ssim2dB (common.cpp:232-240) */
+double ssim2dB(double ssim)
+{
+    const double inv = 1 - ssim;
+    if (inv <= 0.0000000001) return 100;        /* at most 100 dB */
+    return -10.0 * log10(inv);
+}
+/* members of x265_stats and x265_sliceType_stats that oracle/gen_abi_layout.cpp does not list, from the anchors it does: four doubles from globalPsnrY on, then globalSsim;
+ * psnrY / U / V in a row, then ssim (tests/native/abi_layout_quality_check.cpp pins them against the reference's header) */
+enum { STATS_globalPsnrU = X265ABI_STATS_globalPsnrY + 8, STATS_globalPsnrV = X265ABI_STATS_globalPsnrY + 16, STATS_globalPsnr = X265ABI_STATS_globalPsnrY + 24,
+       SLICESTATS_psnrU = X265ABI_SLICESTATS_psnrY + 8, SLICESTATS_psnrV = X265ABI_SLICESTATS_psnrY + 16 };
+static_assert(STATS_globalPsnr + 8 == X265ABI_STATS_globalSsim && SLICESTATS_psnrV + 8 == X265ABI_SLICESTATS_ssim, "x265_stats: the PSNR members lie between the anchors");
+/* x265_encoder_get_stats (Encoder::fetchStats, encoder.cpp:2910-2971): what this encoder counts -- pictures, bits and average QP by slice type, the times and the bit rate;
+ * with --psnr / --ssim the sums of the pictures' values (globalPsnrY / U / V are SUMS there, globalPsnr and globalSsim means; per type: means, the SSIM in dB); with
+ * --max-cll the measured light levels.  The weighted-frame count stays 0. */
 void abi_encoder_get_stats(void* enc, void* stats, uint32_t bytes)
 {
     if (!stats) return;
@@ -533,8 +555,8 @@ void abi_encoder_get_stats(void* enc, void* stats, uint32_t bytes)
     if (enc)
     {
         AbiEncoder& a = *(AbiEncoder*)enc;
-        uint64_t w[13] = { 0 };
-        if (x265amd_encoder_stats(a.enc, w, 13) == 0)
+        uint64_t w[31] = { 0 };
+        if (x265amd_encoder_stats(a.enc, w, 31) == 0)
         {
             uint64_t pics = 0, bits = 0;
             static const size_t at[3] = { X265ABI_STATS_statsI, X265ABI_STATS_statsP, X265ABI_STATS_statsB };
@@ -549,6 +571,13 @@ void abi_encoder_get_stats(void* enc, void* stats, uint32_t bytes)
                     wr<double>(st, at[t] + X265ABI_SLICESTATS_avgQp, qsum / (double)n);
                     /* EncStats: bitrate of the type's pictures at the frame rate, in kbps (encoder.cpp:2885: m_accBits * scale / m_numPics, scale = fps / 1000) */
                     wr<double>(st, at[t] + X265ABI_SLICESTATS_bitrate, (double)w[7 + t] * a.fps / 1000.0 / (double)n);
+                    double q[4]; memcpy(q, &w[17 + 4 * t], 32);
+                    if (a.psnr)
+                    {
+                        wr<double>(st, at[t] + X265ABI_SLICESTATS_psnrY, q[0] / (double)n); wr<double>(st, at[t] + SLICESTATS_psnrU, q[1] / (double)n);
+                        wr<double>(st, at[t] + SLICESTATS_psnrV, q[2] / (double)n);
+                    }
+                    if (a.ssim) wr<double>(st, at[t] + X265ABI_SLICESTATS_ssim, ssim2dB(q[3] / (double)n));
                 }
             }
             struct timespec now; clock_gettime(CLOCK_MONOTONIC, &now);
@@ -557,11 +586,60 @@ void abi_encoder_get_stats(void* enc, void* stats, uint32_t bytes)
             wr<double>(st, X265ABI_STATS_elapsedEncodeTime, elapsed); wr<double>(st, X265ABI_STATS_elapsedVideoTime, video);
             wr<double>(st, X265ABI_STATS_bitrate, video > 0 ? 0.001 * (double)bits / video : 0.0);
             wr<uint64_t>(st, X265ABI_STATS_accBits, bits); wr<uint32_t>(st, X265ABI_STATS_encodedPictureCount, (uint32_t)pics);
+            double all[4]; memcpy(all, &w[13], 32);
+            if (a.psnr)
+            {
+                wr<double>(st, X265ABI_STATS_globalPsnrY, all[0]); wr<double>(st, STATS_globalPsnrU, all[1]); wr<double>(st, STATS_globalPsnrV, all[2]);
+                if (pics) wr<double>(st, STATS_globalPsnr, (all[0] * 6 + all[1] + all[2]) / (8 * (uint32_t)pics));
+            }
+            if (a.ssim && pics) wr<double>(st, X265ABI_STATS_globalSsim, all[3] / (uint32_t)pics);
+            if (a.levels && pics)
+            {
+                double fall; memcpy(&fall, &w[30], 8);
+                wr<uint16_t>(st, X265ABI_STATS_maxCLL, (uint16_t)w[29]); wr<uint16_t>(st, X265ABI_STATS_maxFALL, (uint16_t)(fall / (uint32_t)pics));
+            }
         }
     }
     memcpy(stats, st, bytes < (uint32_t)X265ABI_SIZEOF_STATS ? bytes : (uint32_t)X265ABI_SIZEOF_STATS);
 }
-void abi_encoder_log(void*, int, char**) {}
+/* x265_encoder_log -> Encoder::printSummary (encoder.cpp:2666-2757) when a quality metric is on: the `frame I / P / B:` lines of statsString and the `encoded` line, in the
+ * reference's text, on stderr.  With both metrics off nothing is printed, as before they were built. */
+void abi_encoder_log(void* enc, int, char**)
+{
+    if (!enc) return;
+    AbiEncoder& a = *(AbiEncoder*)enc;
+    if (!a.psnr && !a.ssim) return;
+    uint64_t w[31] = { 0 };
+    if (x265amd_encoder_stats(a.enc, w, 31) != 0) return;
+    uint64_t pics = 0, bits = 0;
+    double qpAll = 0;
+    static const char* const names[3] = { "I", "P", "B" };
+    for (int t = 0; t < 3; t++)
+    {
+        const uint64_t n = w[4 + t];
+        double qsum, q[4]; memcpy(&qsum, &w[10 + t], 8); memcpy(q, &w[17 + 4 * t], 32);
+        pics += n; bits += w[7 + t]; qpAll += qsum;
+        if (!n) continue;
+        char buffer[200];
+        int len = sprintf(buffer, "%6u, ", (unsigned)n);
+        len += sprintf(buffer + len, "Avg QP:%2.2lf", qsum / (double)n);
+        len += sprintf(buffer + len, "  kb/s: %-8.2lf", (double)w[7 + t] * (a.fps / 1000 / (double)n));
+        if (a.psnr) len += sprintf(buffer + len, "  PSNR Mean: Y:%.3lf U:%.3lf V:%.3lf", q[0] / (double)n, q[1] / (double)n, q[2] / (double)n);
+        if (a.ssim) sprintf(buffer + len, "  SSIM Mean: %.6lf (%.3lfdB)", q[3] / (double)n, ssim2dB(q[3] / (double)n));
+        fprintf(stderr, "x265amd [info]: frame %s: %s\n", names[t], buffer);
+    }
+    if (!pics) { fprintf(stderr, "\nencoded 0 frames\n"); return; }
+    struct timespec now; clock_gettime(CLOCK_MONOTONIC, &now);
+    const double elapsed = (double)(now.tv_sec - a.opened.tv_sec) + 1e-9 * (double)(now.tv_nsec - a.opened.tv_nsec);
+    const double video = (double)pics / a.fps;
+    double all[4]; memcpy(all, &w[13], 32);
+    char buffer[300];
+    int p = sprintf(buffer, "\nencoded %d frames in %d:%02d:%05.2f (%.2f fps), %.2f kb/s, Avg QP:%2.2lf", (int)pics, (int)elapsed / 3600, (int)(elapsed / 60) % 60,
+                    (int)elapsed % 60 + (elapsed - (int)elapsed), (double)pics / elapsed, (0.001f * (double)bits) / video, qpAll / (double)pics);
+    if (a.psnr) p += sprintf(buffer + p, ", Global PSNR: %.3f", (all[0] * 6 + all[1] + all[2]) / (8 * (uint32_t)pics));
+    if (a.ssim) p += sprintf(buffer + p, ", SSIM Mean Y: %.7f (%6.3f dB)", all[3] / (double)pics, ssim2dB(all[3] / (double)pics));
+    fprintf(stderr, "%s\n", buffer);
+}
 void abi_encoder_close(void* enc)
 {
     if (!enc) return;
@@ -612,16 +690,28 @@ void abi_csvlog_encode(const void* p, const void* stats, int, int, int argc, cha
     const double elapsed = rd<double>(stats, X265ABI_STATS_elapsedEncodeTime);
     const uint32_t pics = rd<uint32_t>(stats, X265ABI_STATS_encodedPictureCount);
     fprintf(f, "%.2f, %.2f, %.2f,", elapsed, elapsed > 0 ? pics / elapsed : 0.0, rd<double>(stats, X265ABI_STATS_bitrate));
-    fprintf(f, " -, -, -, -,");          /* PSNR: not measured */
-    fprintf(f, " -, -,");                /* SSIM */
+    const bool psnr = PI(p, bEnablePsnr) != 0, ssim = PI(p, bEnableSsim) != 0;          /* (the client passes the param x265_encoder_parameters filled: configure's switches) */
+    if (psnr)
+        fprintf(f, " %.3lf, %.3lf, %.3lf, %.3lf,", rd<double>(stats, X265ABI_STATS_globalPsnrY) / pics, rd<double>(stats, STATS_globalPsnrU) / pics,
+                rd<double>(stats, STATS_globalPsnrV) / pics, rd<double>(stats, STATS_globalPsnr));
+    else fprintf(f, " -, -, -, -,");
+    if (ssim) fprintf(f, " %.6f, %6.3f,", rd<double>(stats, X265ABI_STATS_globalSsim), ssim2dB(rd<double>(stats, X265ABI_STATS_globalSsim)));
+    else fprintf(f, " -, -,");
     static const size_t at[3] = { X265ABI_STATS_statsI, X265ABI_STATS_statsP, X265ABI_STATS_statsB };
     for (int t = 0; t < 3; t++)
     {
         const uint32_t n = rd<uint32_t>(stats, at[t] + X265ABI_SLICESTATS_numPics);
-        if (n) fprintf(f, " %-6u, %2.2lf, %-8.2lf, -, -, -, -,", n, rd<double>(stats, at[t] + X265ABI_SLICESTATS_avgQp), rd<double>(stats, at[t] + X265ABI_SLICESTATS_bitrate));
+        if (n)
+        {
+            fprintf(f, " %-6u, %2.2lf, %-8.2lf,", n, rd<double>(stats, at[t] + X265ABI_SLICESTATS_avgQp), rd<double>(stats, at[t] + X265ABI_SLICESTATS_bitrate));
+            if (psnr) fprintf(f, " %.3lf, %.3lf, %.3lf,", rd<double>(stats, at[t] + X265ABI_SLICESTATS_psnrY), rd<double>(stats, at[t] + SLICESTATS_psnrU), rd<double>(stats, at[t] + SLICESTATS_psnrV));
+            else fprintf(f, " -, -, -,");
+            if (ssim) fprintf(f, " %.3lf,", rd<double>(stats, at[t] + X265ABI_SLICESTATS_ssim));
+            else fprintf(f, " -,");
+        }
         else fprintf(f, " -, -, -, -, -, -, -,");
     }
-    if (rd<uint16_t>(p, X265ABI_PARAM_maxCLL) || rd<uint16_t>(p, X265ABI_PARAM_maxFALL)) fprintf(f, " %-6u, %-6u,", 0u, 0u);
+    if (rd<uint16_t>(p, X265ABI_PARAM_maxCLL) || rd<uint16_t>(p, X265ABI_PARAM_maxFALL)) fprintf(f, " %-6u, %-6u,", (unsigned)rd<uint16_t>(stats, X265ABI_STATS_maxCLL), (unsigned)rd<uint16_t>(stats, X265ABI_STATS_maxFALL));
     fprintf(f, " %s\n", g_versionStr);
 }
 void abi_dither_image(void*, int, int, int16_t*, int) {}

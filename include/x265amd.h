@@ -587,6 +587,29 @@ int x265amd_extend_border_band_420(void* stream, x265amd_pixel* d_y, x265amd_pix
 int x265amd_weight_plane(void* stream, const x265amd_pixel* d_src, x265amd_pixel* d_dst, intptr_t stride, int width, int height,
                          int marginX, int marginY, int inputWeight, int inputOffset, int log2WeightDenom);
 
+/* --- picture ingest: a caller's surface becomes the padded source picture in ONE launch (csrc/ingest_kernels.hip).
+ * What PicYuv::copyFromPicture (source/common/picyuv.cpp:261-515) and extendPicBorder make of an x265_picture, per destination sample of the padded area:
+ *     dst(x, y) = conv(src(clamp(x, 0, srcW - 1), clamp(y, 0, srcH - 1))),   x in [-marginX, W + marginX), y in [-marginY, H + marginY)
+ * (the chroma planes with half of everything), conv by (bitDepth, X265AMD_DEPTH) as copyFromPicture chooses it (csrc/ingest_dev.h), luma then clipped to
+ * [clipMin, clipMax] when either is set.  d_pic is the flat Y | U | V buffer of the encoder: plane strides W + 2 marginX and W / 2 + marginX, (H + 2 marginY) and
+ * (H / 2 + marginY) rows, chroma margins marginX / 2 and marginY / 2; every element of it is written (with odd margins the few elements outside the padded area: zero).
+ * Refused by name before any launch: a null plane, a depth outside 8..16, a stride below the row's bytes, an odd stride or address with 16-bit samples, odd srcW / srcH,
+ * W < srcW, bounds outside the pixel range or crossed.  x265amd_ingest_model: the same on host memory, plain loops (host/ingest_model.cpp; loads without a GPU). */
+#ifndef X265AMD_SURFACE_DEFINED
+#define X265AMD_SURFACE_DEFINED
+typedef struct x265amd_surface {
+    const void* planes[3];      /* planar: Y, U, V; semi-planar: Y, UV, unused */
+    int32_t stride[3];          /* bytes */
+    int32_t bitDepth;           /* 8..16: the depth of the samples as x265_picture.bitDepth says it (16 for P010 / P016) */
+    int32_t layout;             /* 0 planar 4:2:0, 1 semi-planar 4:2:0 */
+    int32_t clipMin, clipMax;   /* luma bounds after conversion; -1 = none */
+    int32_t reserved;
+} x265amd_surface;
+#endif
+int x265amd_ingest_picture(void* stream, const x265amd_surface* d_src, int srcW, int srcH,
+                           x265amd_pixel* d_pic /* flat Y|U|V buffer */, int W, int H, int marginX, int marginY);
+int x265amd_ingest_model(const x265amd_surface* src, int srcW, int srcH, x265amd_pixel* pic, int W, int H, int marginX, int marginY);
+
 /* --- in-loop deblocking of a picture: Deblock::deblockCTU over all CTUs (reference:
  * source/common/deblock.cpp:37-510; sample filters deblock.cpp:268-310 and source/common/loopfilter.cpp:140-180), 4:2:0.
  * The picture's coding data is one record per 4x4 unit in raster order ((width/4) x (height/4); what the per-CTU CUData arrays

@@ -181,6 +181,24 @@ int x265amd_encoder_encode(x265amd_encoder* enc, x265amd_nal** pp_nal, uint32_t*
  * holds host pointers, x265.h:397-490): this is the form for callers whose frames are made or decoded on the GPU, and the one bench.py times ("inputs already resident in
  * HBM when the timed region starts").  Everything else -- pic_out, the NAL units, flushing with pic_in == NULL -- as x265amd_encoder_encode. */
 int x265amd_encoder_encode_device(x265amd_encoder* enc, x265amd_nal** pp_nal, uint32_t* pi_nal, const x265amd_picture* pic_in, x265amd_picture* pic_out);
+/* The same call for an input picture AS IT COMES: any sample depth from 8 to 16 bits (x265_picture.bitDepth; 16 for the MSB-aligned words of P010 / P016), three planes
+ * or NV12-style luma + interleaved U,V, with luma bounds (--min-luma / --max-luma).  One launch (x265amd_ingest_picture, include/x265amd.h) converts the samples as
+ * PicYuv::copyFromPicture does (source/common/picyuv.cpp:298-424), pads the picture to the coded size and fills the margins.  on_device != 0: in->planes are device
+ * addresses -- what a GPU decoder hands over.  Otherwise host memory: the caller's bytes go as they are, strides included, through a pinned buffer of the encoder's into
+ * device memory (one copy per plane) and are converted there.  The picture is srcWidth x srcHeight of x265amd_param.  Everything else as x265amd_encoder_encode
+ * (in == NULL flushes).  The same-depth planar forms above are untouched by this entry point. */
+#ifndef X265AMD_SURFACE_DEFINED
+#define X265AMD_SURFACE_DEFINED
+typedef struct x265amd_surface {
+    const void* planes[3];      /* planar: Y, U, V; semi-planar: Y, UV, unused */
+    int32_t stride[3];          /* bytes */
+    int32_t bitDepth;           /* 8..16: the depth of the samples as x265_picture.bitDepth says it (16 for P010 / P016) */
+    int32_t layout;             /* 0 planar 4:2:0, 1 semi-planar 4:2:0 */
+    int32_t clipMin, clipMax;   /* luma bounds after conversion; -1 = none */
+    int32_t reserved;
+} x265amd_surface;
+#endif
+int x265amd_encoder_encode_surface(x265amd_encoder* enc, x265amd_nal** pp_nal, uint32_t* pi_nal, const x265amd_surface* in, int on_device, x265amd_picture* pic_out);
 void x265amd_encoder_close(x265amd_encoder* enc);
 
 /* ---- frame-per-GPU: a finished CTU row travels from the object that codes a picture to the objects that reference it ----

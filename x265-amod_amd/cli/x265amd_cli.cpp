@@ -9,9 +9,11 @@
  *             --scenecut N --no-scenecut --[no-]hist-scenecut --rc-lookahead N --lookahead-slices N --ref N --limit-refs N --rd N --rdoq-level N --psy-rd F --psy-rdoq F --me name --subme N
  *             --merange N --max-merge N --[no-]rect --[no-]amp --[no-]limit-modes --[no-]early-skip --rskip N (0, 1, 2) --rskip-edge-threshold N --[no-]weightp --[no-]weightb --[no-]sao --[no-]deblock --[no-]wpp
  *             --tu-intra-depth N --tu-inter-depth N --[no-]signhide --[no-]strong-intra-smoothing --[no-]temporal-mvp --[no-]b-intra --[no-]fast-intra --[no-]info --[no-]psnr --[no-]ssim --max-cll C,F
- *             --frame-threads N --pools S ...]
+ *             --frame-threads N --pools S --min-luma N --max-luma N ...] [-D|--output-depth 8|10] [--dither]
  *
- * Input: YUV4MPEG2, 4:2:0, 8 or 10 bits (source/input/y4m.cpp:150-330 header, :405-441 frames).  Output: the Annex-B stream (source/output/raw.cpp); the reconstruction in
+ * Input: YUV4MPEG2, 4:2:0, 8, 10, 12, 14 or 16 bits (source/input/y4m.cpp:150-330 header, :405-441 frames).  -D / --output-depth chooses the library (without it: the 10-bit
+ * library for inputs above 8 bits); a picture of another depth than the library's is converted by the library as PicYuv::copyFromPicture converts it, or with --dither by
+ * x265_dither_image first (abrEncApp.cpp:581-618).  --input-depth is accepted and ignored: the y4m header says the depth.  Output: the Annex-B stream (source/output/raw.cpp); the reconstruction in
  * display order as raw planar samples (source/output/yuv.cpp) or, for a name ending in .y4m, as YUV4MPEG2 (source/output/y4m.cpp: stream header once, "FRAME\n" before each
  * picture); --csv: the summary line of the reference's CSV log at its default level (x265_csvlog_open / x265_csvlog_encode through the table).
  * x265_picture / x265_nal are touched through the member offsets generated from the reference's header (host/x265_abi_layout.h: numbers only).  Host C++ only. */
@@ -72,7 +74,7 @@ bool loadApi(Api& a, const std::string& dir, int depth)
 
 struct Y4m { FILE* f = nullptr; int width = 0, height = 0, depth = 8; uint32_t fpsNum = 25, fpsDen = 1; int sarW = 0, sarH = 0; size_t frameBytes = 0; };
 
-/* YUV4MPEG2 stream header: space separated tags W H F I A C X (y4m.cpp:150-330); only 4:2:0 at 8 or 10 bits is accepted here */
+/* YUV4MPEG2 stream header: space separated tags W H F I A C X (y4m.cpp:150-330); only 4:2:0 at 8, 10, 12, 14 or 16 bits is accepted here */
 bool openY4m(Y4m& y, const char* path)
 {
     y.f = fopen(path, "rb");
@@ -98,8 +100,8 @@ bool openY4m(Y4m& y, const char* path)
         default: break;
         }
     }
-    if (csp != 420 || (y.depth != 8 && y.depth != 10) || y.width <= 0 || y.height <= 0 || !y.fpsNum || !y.fpsDen)
-    { fprintf(stderr, "x265amd: unsupported y4m stream (4:2:0, 8 or 10 bits only)\n"); return false; }
+    if (csp != 420 || (y.depth != 8 && y.depth != 10 && y.depth != 12 && y.depth != 14 && y.depth != 16) || y.width <= 0 || y.height <= 0 || !y.fpsNum || !y.fpsDen)
+    { fprintf(stderr, "x265amd: unsupported y4m stream (4:2:0 at 8, 10, 12, 14 or 16 bits only)\n"); return false; }
     y.frameBytes = (size_t)y.width * y.height * 3 / 2 * (y.depth > 8 ? 2 : 1);
     return true;
 }
@@ -120,7 +122,8 @@ bool endsWith(const std::string& s, const char* tail) { const size_t n = strlen(
 int main(int argc, char** argv)
 {
     const char* input = nullptr; const char* output = nullptr; const char* recon = nullptr; const char* preset = nullptr; const char* tune = nullptr; const char* csv = nullptr;
-    int frames = 0;
+    int frames = 0, outputDepth = 0;
+    bool dither = false;
     std::vector<std::pair<std::string, const char*>> opts;         /* every other option, with the argument behind it if there is one */
     bool lastGeneric = false;
     for (int i = 1; i < argc; i++)
@@ -134,7 +137,9 @@ int main(int argc, char** argv)
         else if (a == "--preset" || a == "-p") preset = val();
         else if (a == "--tune" || a == "-t") tune = val();
         else if (a == "--csv") csv = val();
-        else if (a == "--input-depth" || a == "--output-depth" || a == "-D") (void)val();         /* the depth is the input file's and the library's */
+        else if (a == "--input-depth") (void)val();         /* the depth is the input file's: the y4m header says it */
+        else if (a == "--output-depth" || a == "-D") outputDepth = atoi(val());
+        else if (a == "--dither") dither = true;
         else if (a == "--no-progress" || a == "--progress") { }
         else if (a == "-F") opts.push_back({ "--frame-threads", val() });
         else if (a.rfind("--", 0) == 0) { opts.push_back({ a, nullptr }); lastGeneric = true; continue; }
@@ -150,8 +155,10 @@ int main(int argc, char** argv)
     const size_t slash = dir.find_last_of('/');
     dir = (slash == std::string::npos ? std::string(".") : dir.substr(0, slash)) + "/../lib";
     if (const char* e = getenv("X265AMD_LIBDIR")) dir = e;
+    if (outputDepth && outputDepth != 8 && outputDepth != 10) { fprintf(stderr, "x265amd: --output-depth: 8 or 10\n"); return 2; }
+    const int libDepth = outputDepth ? outputDepth : (y.depth > 8 ? 10 : 8);
     Api api;
-    if (!loadApi(api, dir, y.depth)) return 1;
+    if (!loadApi(api, dir, libDepth)) return 1;
 
     void* p = api.param_alloc();
     if (!p || api.param_default_preset(p, preset, tune) < 0) { fprintf(stderr, "x265amd: preset %s / tune %s is not known\n", preset ? preset : "(default)", tune ? tune : "(none)"); return 2; }
@@ -180,7 +187,7 @@ int main(int argc, char** argv)
     if (recY4m)
     {
         /* output/y4m.cpp: the stream header once; every picture is "FRAME\n" + its samples, written at its place in display order */
-        recHeader = (size_t)fprintf(rec, "YUV4MPEG2 W%d H%d F%u:%u Ip C420%s\n", y.width, y.height, y.fpsNum, y.fpsDen, y.depth > 8 ? "p10" : "");
+        recHeader = (size_t)fprintf(rec, "YUV4MPEG2 W%d H%d F%u:%u Ip C420%s\n", y.width, y.height, y.fpsNum, y.fpsDen, libDepth > 8 ? "p10" : "");
     }
     Nal* nal = nullptr; uint32_t nnal = 0;
     /* the parameter sets once in front -- unless the encoder repeats them with every keyframe (x265.cpp: the program asks x265_encoder_parameters what configure made of it) */
@@ -191,8 +198,11 @@ int main(int argc, char** argv)
         for (uint32_t i = 0; i < nnal; i++) fwrite(nal[i].payload, 1, nal[i].sizeBytes, out);
     }
 
-    const int isz = y.depth > 8 ? 2 : 1;
+    const int isz = y.depth > 8 ? 2 : 1, osz = libDepth > 8 ? 2 : 1;        /* bytes per sample of the input file and of the reconstruction */
+    const size_t recFrameBytes = (size_t)y.width * y.height * 3 / 2 * osz;
     std::vector<uint8_t> buf;
+    /* --dither (abrEncApp.cpp:581-618): an error row of width + 1 values, used only for pictures deeper than the library */
+    std::vector<int16_t> errorBuf(dither ? (size_t)y.width + 1 : 0, 0);
     void* picIn = api.picture_alloc();
     void* picOut = api.picture_alloc();
     api.picture_init(p, picIn); api.picture_init(p, picOut);
@@ -203,13 +213,13 @@ int main(int argc, char** argv)
         if (rec)
         {
             /* the reconstruction file is in display order (output/yuv.cpp, y4m.cpp write each picture at poc * frame size; x265_picture.poc counts from the first picture on) */
-            const size_t place = (size_t)rd<int32_t>(picOut, X265ABI_PIC_poc), frameSize = y.frameBytes + (recY4m ? 6 : 0);
+            const size_t place = (size_t)rd<int32_t>(picOut, X265ABI_PIC_poc), frameSize = recFrameBytes + (recY4m ? 6 : 0);
             fseek(rec, (long)(recHeader + place * frameSize), SEEK_SET);
             if (recY4m) fwrite("FRAME\n", 1, 6, rec);
             for (int k = 0; k < 3; k++)
             {
                 const uint8_t* plane = rd<const uint8_t*>(picOut, X265ABI_PIC_planes + 8 * k);
-                const int stride = rd<int32_t>(picOut, X265ABI_PIC_stride + 4 * k), w = (k ? y.width / 2 : y.width) * isz, h = k ? y.height / 2 : y.height;
+                const int stride = rd<int32_t>(picOut, X265ABI_PIC_stride + 4 * k), w = (k ? y.width / 2 : y.width) * osz, h = k ? y.height / 2 : y.height;
                 for (int r = 0; r < h; r++) fwrite(plane + (size_t)r * stride, 1, (size_t)w, rec);
             }
         }
@@ -220,6 +230,12 @@ int main(int argc, char** argv)
         uint8_t* planes[3] = { buf.data(), buf.data() + (size_t)y.width * y.height * isz, buf.data() + (size_t)y.width * y.height * isz * 5 / 4 };
         const int strides[3] = { y.width * isz, y.width / 2 * isz, y.width / 2 * isz };
         for (int k = 0; k < 3; k++) { wr<void*>(picIn, X265ABI_PIC_planes + 8 * k, planes[k]); wr<int32_t>(picIn, X265ABI_PIC_stride + 4 * k, strides[k]); }
+        wr<int32_t>(picIn, X265ABI_PIC_bitDepth, y.depth);
+        if (dither && y.depth > libDepth)
+        {
+            ((void (*)(void*, int, int, int16_t*, int))api.t->fn2[7])(picIn, y.width, y.height, errorBuf.data(), libDepth);
+            wr<int32_t>(picIn, X265ABI_PIC_bitDepth, libDepth);
+        }
         wr<int64_t>(picIn, X265ABI_PIC_pts, (int64_t)read);
         read++;
         rc = api.encoder_encode(enc, &nal, &nnal, picIn, rec ? picOut : nullptr);

@@ -9,6 +9,7 @@
  *   - per frame: FrameEncoder::compressFrame (analysis rows, deblocking, SAO, border extension, slice NAL)   source/encoder/frameencoder.cpp:470-1130
  * Pictures (source and reconstruction) are padded planes in device memory with the reference's PicYuv margins (maxCUSize + 32 / + 16). */
 #include "encoder_impl.h"
+#include "ingest_dev.h"
 
 /* ---- configuration ---- */
 extern "C" void x265amd_param_default(x265amd_param* p)
@@ -578,7 +579,67 @@ int x265amd_encoder::uploadPicture(const x265amd_picture* in, Pic& pic, bool onD
     return 0;
 }
 
-static int encoder_encode_impl(x265amd_encoder* e, x265amd_nal** ppNal, uint32_t* piNal, const x265amd_picture* picIn, x265amd_picture* picOut, bool inputOnDevice);
+/* The surface form of the input (x265amd_encoder_encode_surface): pic.dSrc whole -- picture area, pad, margins -- from ONE launch of x265amd_ingest_picture, which converts
+ * the samples on the way (PicYuv::copyFromPicture, picyuv.cpp:298-424).  A host surface's planes travel as the caller has them, strides and all: into the encoder's pinned
+ * buffer, from there with one hipMemcpyAsync each into a device copy that the pass reads.  Nothing is padded or converted on the host. */
+int x265amd_encoder::ingestSurface(const x265amd_surface* in, Pic& pic, bool onDevice)
+{
+    if (xa_scratch_alloc((void**)&pic.dSrc, picElems * sizeof(pixel)) != hipSuccess || xa_scratch_alloc((void**)&pic.dRec, picElems * sizeof(pixel)) != hipSuccess)
+        return xa_fail(X265AMD_EHIP, "encoder_encode_surface: device allocation");
+    x265amd_surface dev = *in;
+    uint8_t* raw = nullptr;
+    if (!onDevice)
+    {
+        const int isz = in->bitDepth > 8 ? 2 : 1, nplanes = in->layout ? 2 : 3;
+        size_t at[3] = { 0, 0, 0 }, bytes[3] = { 0, 0, 0 }, total = 0;
+        for (int k = 0; k < nplanes; k++)
+        {
+            const int rows = k ? srcH / 2 : srcH, rowBytes = (k == 0 || in->layout ? srcW : srcW / 2) * isz;
+            at[k] = total; bytes[k] = (size_t)in->stride[k] * (rows - 1) + rowBytes;
+            total += (bytes[k] + 255) & ~(size_t)255;
+        }
+        if (total > ingestPinnedBytes)
+        {
+            if (ingestPinned) (void)hipHostFree(ingestPinned);
+            ingestPinned = nullptr; ingestPinnedBytes = 0;
+            if (hipHostMalloc((void**)&ingestPinned, total, hipHostMallocDefault) != hipSuccess) { ingestPinned = nullptr; return xa_fail(X265AMD_EHIP, "encoder_encode_surface: pinned input buffer"); }
+            ingestPinnedBytes = total;
+        }
+        if (xa_scratch_alloc((void**)&raw, total) != hipSuccess) return xa_fail(X265AMD_EHIP, "encoder_encode_surface: device allocation");
+        for (int k = 0; k < nplanes; k++)
+        {
+            memcpy(ingestPinned + at[k], in->planes[k], bytes[k]);
+            if (hipMemcpyAsync(raw + at[k], ingestPinned + at[k], bytes[k], hipMemcpyHostToDevice, nullptr) != hipSuccess) { xa_scratch_free(raw); return xa_fail(X265AMD_EHIP, "encoder_encode_surface: upload"); }
+            dev.planes[k] = raw + at[k];
+        }
+    }
+    int rc = x265amd_ingest_picture(nullptr, &dev, srcW, srcH, (x265amd_pixel*)pic.dSrc, W, H, marginX, marginY);
+    if (rc == X265AMD_OK && hipMemsetAsync(pic.dRec, 0, picElems * sizeof(pixel), nullptr) != hipSuccess) rc = xa_fail(X265AMD_EHIP, "encoder_encode_surface: memset");
+    if (rc == X265AMD_OK && frameParallel && p.bEnableSAO)
+    {
+        if (xa_scratch_alloc((void**)&pic.dFin, picElems * sizeof(pixel)) != hipSuccess) rc = xa_fail(X265AMD_EHIP, "encoder_encode_surface: device allocation");
+        else if (hipMemsetAsync(pic.dFin, 0, picElems * sizeof(pixel), nullptr) != hipSuccess) rc = xa_fail(X265AMD_EHIP, "encoder_encode_surface: memset");
+    }
+    /* the frame tasks run on their own non-blocking streams: the picture is in place before one can start (and the pinned buffer and the device copy are free again) */
+    if (hipStreamSynchronize(nullptr) != hipSuccess && rc == X265AMD_OK) rc = xa_fail(X265AMD_EHIP, "encoder_encode_surface: the input picture is not memory this device can read");
+    xa_scratch_free(raw);
+    return rc == X265AMD_OK ? 0 : -1;
+}
+
+static int encoder_encode_impl(x265amd_encoder* e, x265amd_nal** ppNal, uint32_t* piNal, const x265amd_picture* picIn, x265amd_picture* picOut, bool inputOnDevice,
+                               const x265amd_surface* surfIn = nullptr);
+extern "C" int x265amd_encoder_encode_surface(x265amd_encoder* e, x265amd_nal** ppNal, uint32_t* piNal, const x265amd_surface* in, int onDevice, x265amd_picture* picOut)
+{
+    /* what the pass would refuse is refused here, by name, before the picture takes a place in display order */
+    if (e && in)
+        if (const char* bad = xa_ingest_check(in, e->srcW, e->srcH, e->W, e->H, e->marginX, e->marginY))
+        {
+            static thread_local char why[160];
+            snprintf(why, sizeof(why), "encoder_encode_surface: %s", bad);
+            return xa_fail(X265AMD_EINVAL, why), -1;
+        }
+    return encoder_encode_impl(e, ppNal, piNal, nullptr, picOut, onDevice != 0, in);
+}
 extern "C" int x265amd_encoder_encode(x265amd_encoder* e, x265amd_nal** ppNal, uint32_t* piNal, const x265amd_picture* picIn, x265amd_picture* picOut)
 {
     return encoder_encode_impl(e, ppNal, piNal, picIn, picOut, false);
@@ -587,18 +648,20 @@ extern "C" int x265amd_encoder_encode_device(x265amd_encoder* e, x265amd_nal** p
 {
     return encoder_encode_impl(e, ppNal, piNal, picIn, picOut, true);
 }
-static int encoder_encode_impl(x265amd_encoder* e, x265amd_nal** ppNal, uint32_t* piNal, const x265amd_picture* picIn, x265amd_picture* picOut, bool inputOnDevice)
+static int encoder_encode_impl(x265amd_encoder* e, x265amd_nal** ppNal, uint32_t* piNal, const x265amd_picture* picIn, x265amd_picture* picOut, bool inputOnDevice,
+                               const x265amd_surface* surfIn)
 {
     if (!e) return xa_fail(X265AMD_EINVAL, "encoder_encode: null encoder");
     if (ppNal) *ppNal = nullptr;
     if (piNal) *piNal = 0;
-    if (picIn)
+    const bool haveInput = picIn || surfIn;
+    if (haveInput)
     {
         PicP pic(new Pic);
         pic->pool = e->laPool;
         pic->poc = e->frameCount++;
         const auto tu0 = std::chrono::steady_clock::now();
-        int rc = e->uploadPicture(picIn, *pic, inputOnDevice);
+        int rc = surfIn ? e->ingestSurface(surfIn, *pic, inputOnDevice) : e->uploadPicture(picIn, *pic, inputOnDevice);
         if (rc) return -1;
         if (e->measuresLevel() && e->measureLevel(*pic)) return -1;
         const auto tl0 = std::chrono::steady_clock::now();
@@ -607,7 +670,7 @@ static int encoder_encode_impl(x265amd_encoder* e, x265amd_nal** ppNal, uint32_t
         e->laInitMs += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tl0).count();
         e->input.push_back(pic);
     }
-    const bool flushing = picIn == nullptr;
+    const bool flushing = !haveInput;
     /* The slice-type decisions.  With pictures coming in, whatever a full queue allows.  When the caller flushes, ONE mini-GOP at a time (below): each decision of
      * the lookahead takes as long as a P picture, and the pictures of the first mini-GOP have no reason to wait for the decisions about the last -- a clip shorter than
      * the lookahead is decided entirely while it is flushed, and its first P picture used to start when the last decision was made.  The decisions themselves do not depend on
@@ -719,7 +782,7 @@ static int encoder_encode_impl(x265amd_encoder* e, x265amd_nal** ppNal, uint32_t
     int waiting = 0;
     for (auto& q : e->inflight) waiting += !q->started;
     /* the caller is held when enough pictures run and enough wait behind them (the lookahead may run ahead of the frame tasks by a window of its own) */
-    const bool mustWait = !picIn || (e->running > e->frameThreads && waiting > 2 * e->p.lookaheadDepth + 8);
+    const bool mustWait = !haveInput || (e->running > e->frameThreads && waiting > 2 * e->p.lookaheadDepth + 8);
     if (!mustWait && front->done.wait_for(std::chrono::seconds(0)) != std::future_status::ready) return 0;
     const int rc = front->done.get();
     e->inflight.pop_front();

@@ -227,6 +227,7 @@ struct x265amd_encoder
         for (auto& q : inflight) if (q->done.valid()) q->done.wait();
         laFieldsFree();
         if (uploadBuf) (void)hipHostFree(uploadBuf);
+        if (ingestPinned) (void)hipHostFree(ingestPinned);
         if (xa_env_present("X265AMD_TIMING") && lookahead)
         {
             fprintf(stderr, "x265amd: input: %.1f ms in uploads; cpu of the picture threads %.1f ms, of the filter threads %.1f ms\n", uploadMs, cpuPictureNs.load() / 1e6, cpuFilterNs.load() / 1e6);
@@ -251,6 +252,10 @@ struct x265amd_encoder
 
     void fillStreamParams(x265amd_stream_params& s) const;
     int uploadPicture(const x265amd_picture* in, Pic& pic, bool onDevice = false);
+    /* x265amd_encoder_encode_surface's counterpart of uploadPicture: any depth, planar or semi-planar, luma bounds -- one launch of x265amd_ingest_picture writes pic.dSrc.
+     * A host surface goes through ingestPinned (the caller's bytes as they are) into a device copy first */
+    int ingestSurface(const x265amd_surface* in, Pic& pic, bool onDevice);
+    uint8_t* ingestPinned = nullptr; size_t ingestPinnedBytes = 0;      /* (hipHostFree in the destructor) */
     void decideMiniGop(bool flush);
     int prepare(const PicP& pic);
     int runFrame(const PicP& pic, std::shared_future<int> prev);

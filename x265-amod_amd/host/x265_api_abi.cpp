@@ -7,7 +7,9 @@
  * reference's header (numbers only) and tests/layout_check.cpp pins against it again; the reference's header itself is not part of this build.
  *
  * Built entries: param_alloc / param_free, picture_alloc / picture_free / picture_init, encoder_open, encoder_parameters, encoder_headers, encoder_encode,
- * encoder_get_stats (with --psnr / --ssim / --max-cll the measured values), encoder_log (the summary lines when a metric is on), encoder_close, cleanup.  Entries of features outside the built subset FAIL CLEANLY: param_default fills the
+ * encoder_get_stats (with --psnr / --ssim / --max-cll the measured values), encoder_log (the summary lines when a metric is on), encoder_close, cleanup, dither_image.
+ * encoder_encode takes x265_picture.bitDepth 8..16 in X265_CSP_I420 or X265_CSP_NV12 form: what is not a planar picture of this library's depth, and every picture under
+ * --min-luma / --max-luma, goes through x265amd_encoder_encode_surface (the ingest pass).  Entries of features outside the built subset FAIL CLEANLY: param_default fills the
  * reference's defaults for the members encoder_open reads and zeroes the rest, param_default_preset accepts NULL / "medium" only (the other presets' option
  * tables are not restated), param_parse / zone_param_parse / scenecut_aware_qp_param_parse report a bad name, encoder_reconfig* / intra_refresh / ctu_info /
  * get_slicetype_poc_and_scenecut / get_ref_frame_list / set_analysis_data return -1, csvlog_open returns NULL.  encoder_open rejects every parameter outside the
@@ -17,6 +19,7 @@
 #include "../../include/x265amd_encoder.h"
 #include "x265_abi_layout.h"
 #include "x265_abi_layout_rskip.h"
+#include "x265_abi_layout_ingest.h"
 #include "x265_api_table.h"
 #include <stdint.h>
 #include <stdio.h>
@@ -51,6 +54,7 @@ struct AbiEncoder
     double fps = 25.0;
     struct timespec opened = { 0, 0 };   /* x265_stats.elapsedEncodeTime counts from encoder_open */
     bool psnr = false, ssim = false, levels = false;    /* what Encoder::configure left of bEnablePsnr / bEnableSsim; maxCLL || maxFALL (fetchStats, encoder.cpp:2962) */
+    int clipMin = -1, clipMax = -1;     /* x265_param.minLuma / maxLuma where they bite (PicYuv::copyFromPicture, picyuv.cpp:413-424): the luma bounds of every surface; -1 = none */
     std::vector<uint8_t> recon;         /* the reconstruction handed out by the last encoder_encode: valid until the next call on this encoder (the reference hands out its own picture) */
 };
 
@@ -78,6 +82,7 @@ void abi_param_default(void* p)
     wr<int32_t>(p, X265ABI_PARAM_bEnableTemporalMvp, 1); wr<int32_t>(p, X265ABI_PARAM_bEnableLoopFilter, 1); wr<int32_t>(p, X265ABI_PARAM_bEnableSAO, 1);
     wr<int32_t>(p, X265ABI_PARAM_rdLevel, 3); wr<int32_t>(p, X265ABI_PARAM_bIntraInBFrames, 1); wr<double>(p, X265ABI_PARAM_psyRd, 2.0); wr<double>(p, X265ABI_PARAM_psyRdoq, 0.0);
     wr<int32_t>(p, X265ABI_PARAM_bEmitCLL, 1); wr<float>(p, X265ABI_PARAM_edgeVarThreshold, 0.05f);
+    wr<uint16_t>(p, X265ABI_PARAM_minLuma, 0); wr<uint16_t>(p, X265ABI_PARAM_maxLuma, (uint16_t)((1 << X265AMD_DEPTH) - 1));          /* PIXEL_MAX (param.cpp:334-335) */
     wr<int32_t>(p, X265ABI_PARAM_vui_videoFormat, 5); wr<int32_t>(p, X265ABI_PARAM_vui_colorPrimaries, 2); wr<int32_t>(p, X265ABI_PARAM_vui_transferCharacteristics, 2);
     wr<int32_t>(p, X265ABI_PARAM_vui_matrixCoeffs, 2);         /* unspecified (param.cpp:358-366) */
     wr<int32_t>(p, X265ABI_PARAM_rc_rateControlMode, 2 /* X265_RC_CRF */); wr<int32_t>(p, X265ABI_PARAM_rc_qp, 32); wr<double>(p, X265ABI_PARAM_rc_ipFactor, 1.4f);
@@ -232,6 +237,9 @@ int abi_param_parse(void* p, const char* name, const char* value)
     /* (param.cpp:1280: atoi(value) / 100.0f -- which the reference's -ffast-math build computes as a float product with 0.01f: "5" gives 0.049999997f, one ulp below the
      * default 0.05f) */
     if (!strcmp(key, "rskip-edge-threshold")) { const int v = num(bad); wr<float>(p, X265ABI_PARAM_edgeVarThreshold, (float)v * 0.01f); return bad ? -2 : 0; }
+    /* (param.cpp:1256-1257: (uint16_t)atoi(value); a missing value is the text "true" -- stored as 0 -- and a bad value, param.cpp:1448) */
+    if (!strcmp(key, "min-luma")) { wr<uint16_t>(p, X265ABI_PARAM_minLuma, (uint16_t)atoi(value ? value : "true")); return value ? 0 : -2; }
+    if (!strcmp(key, "max-luma")) { wr<uint16_t>(p, X265ABI_PARAM_maxLuma, (uint16_t)atoi(value ? value : "true")); return value ? 0 : -2; }
     if (!strcmp(key, "crf")) { const double v = real(bad); if (bad) return -2; wr<double>(p, X265ABI_PARAM_rc_rfConstant, v); wr<int32_t>(p, X265ABI_PARAM_rc_rateControlMode, 2); return 0; }
     if (!strcmp(key, "qp")) { const int v = num(bad); if (bad) return -2; wr<int32_t>(p, X265ABI_PARAM_rc_qp, v); wr<int32_t>(p, X265ABI_PARAM_rc_rateControlMode, 1); return 0; }
     if (!strcmp(key, "bitrate")) { const int v = num(bad); if (bad) return -2; wr<int32_t>(p, X265ABI_PARAM_rc_bitrate, v); wr<int32_t>(p, X265ABI_PARAM_rc_rateControlMode, 0); return 0; }
@@ -391,6 +399,10 @@ void* abi_encoder_open(void* p)
     REQUIRE(!PI(p, bAQMotion) && !PI(p, gopLookahead) && !PI(p, radl) && !PI(p, bEnableSceneCutAwareQp) && !PI(p, bEnableFades), "aq-motion / gop-lookahead / radl / scenecut-aware-qp / fades are not built");
     REQUIRE(PI(p, levelIdc) == 0, "levelIdc: the level is derived (determineLevel), not forced");
     REQUIRE(PI(p, searchMethod) == 0 || PI(p, searchMethod) == 1 || PI(p, searchMethod) == 3 || PI(p, searchMethod) == 5, "searchMethod: only dia, hex, star and full are built (no umh / sea)");
+    /* --min-luma / --max-luma: the bounds every input picture's luma is clipped to (picyuv.cpp:413-424).  A maxLuma of 0 is what a zero-filled x265_param holds, not a bound
+     * anybody asks for (every picture would be black): it counts as not set, like PIXEL_MAX */
+    const int lumaMin = rd<uint16_t>(p, X265ABI_PARAM_minLuma), lumaMax = rd<uint16_t>(p, X265ABI_PARAM_maxLuma);
+    REQUIRE(lumaMin <= (1 << X265AMD_DEPTH) - 1 && lumaMax <= (1 << X265AMD_DEPTH) - 1 && (!lumaMax || lumaMin <= lumaMax), "minLuma / maxLuma outside the pixel range or crossed");
 #undef REQUIRE
     if (bad) { snprintf(why, sizeof(why), "x265_encoder_open: %s", bad); xa_fail(X265AMD_EINVAL, why); return nullptr; }
     x265amd_param q;
@@ -465,6 +477,7 @@ void* abi_encoder_open(void* p)
     a->bframeDelay = q.bframes ? (q.bBPyramid ? 2 : 1) : 0;
     a->param.assign((const uint8_t*)p, (const uint8_t*)p + X265ABI_SIZEOF_PARAM);         /* api.cpp:96-116: the encoder keeps a copy */
     a->psnr = q.bEnablePsnr != 0; a->ssim = q.bEnableSsim != 0; a->levels = q.maxCLL || q.maxFALL;
+    a->clipMin = lumaMin ? lumaMin : -1; a->clipMax = lumaMax && lumaMax != (1 << X265AMD_DEPTH) - 1 ? lumaMax : -1;
     wr<int32_t>(a->param.data(), X265ABI_PARAM_bEnablePsnr, q.bEnablePsnr); wr<int32_t>(a->param.data(), X265ABI_PARAM_bEnableSsim, q.bEnableSsim);
     if ((q.keyframeMax >= 0 && q.keyframeMax <= 1) || q.bEmitHDR10SEI) wr<int32_t>(a->param.data(), X265ABI_PARAM_bRepeatHeaders, 1);          /* ... as Encoder::configure left it: x265_encoder_parameters tells the caller (the reference's program asks before it writes the headers) */
     a->fps = (double)q.fpsNum / (double)q.fpsDenom;
@@ -479,21 +492,35 @@ int abi_encoder_headers(void* enc, x265amd_nal** ppNal, uint32_t* piNal)
 }
 int abi_encoder_encode(void* enc, x265amd_nal** ppNal, uint32_t* piNal, void* picIn, void* picOut)
 {
-    if (!enc) return -1;
-    AbiEncoder& a = *(AbiEncoder*)enc;
     x265amd_picture in, out;
-    memset(&in, 0, sizeof(in)); memset(&out, 0, sizeof(out));
+    x265amd_surface surf;
+    memset(&in, 0, sizeof(in)); memset(&out, 0, sizeof(out)); memset(&surf, 0, sizeof(surf));
+    bool asSurface = false;
     if (picIn)
     {
-        if (rd<int32_t>(picIn, X265ABI_PIC_bitDepth) != X265AMD_DEPTH) { xa_fail(X265AMD_EINVAL, "x265_encoder_encode: picture bit depth differs from the library's (no conversion)"); return -1; }
-        if (rd<int32_t>(picIn, X265ABI_PIC_colorSpace) != 1) { xa_fail(X265AMD_EINVAL, "x265_encoder_encode: only X265_CSP_I420 pictures"); return -1; }
+        /* the picture's form is looked at first, whatever the encoder: any depth PicYuv::copyFromPicture takes (picyuv.cpp:289-396), three planes or -- beyond the reference,
+         * whose x265.h only declares it -- X265_CSP_NV12's luma plane + U,V pairs */
+        const int depth = rd<int32_t>(picIn, X265ABI_PIC_bitDepth), csp = rd<int32_t>(picIn, X265ABI_PIC_colorSpace);
+        if (depth < 8 || depth > 16) { xa_fail(X265AMD_EINVAL, "x265_encoder_encode: picture bitDepth outside 8..16"); return -1; }
+        if (csp != X265ABI_CSP_I420 && csp != X265ABI_CSP_NV12) { xa_fail(X265AMD_EINVAL, "x265_encoder_encode: colorSpace: only X265_CSP_I420 and X265_CSP_NV12 pictures (4:2:0)"); return -1; }
         const int st = rd<int32_t>(picIn, X265ABI_PIC_sliceType);
         if (st != 0) { xa_fail(X265AMD_EINVAL, "x265_encoder_encode: forced slice types are not built (sliceType must be X265_TYPE_AUTO)"); return -1; }
         for (int k = 0; k < 3; k++)
         {
             in.planes[k] = rd<void*>(picIn, X265ABI_PIC_planes + 8 * k);
             in.stride[k] = rd<int32_t>(picIn, X265ABI_PIC_stride + 4 * k);
+            surf.planes[k] = in.planes[k]; surf.stride[k] = in.stride[k];
         }
+        surf.bitDepth = depth; surf.layout = csp == X265ABI_CSP_NV12;
+        if (surf.layout) { surf.planes[2] = nullptr; surf.stride[2] = 0; }
+    }
+    if (!enc) { xa_fail(X265AMD_EINVAL, "x265_encoder_encode: null encoder"); return -1; }
+    AbiEncoder& a = *(AbiEncoder*)enc;
+    if (picIn)
+    {
+        /* the library's depth in three planes with no luma bound goes the way it always went; everything else through the ingest pass */
+        surf.clipMin = a.clipMin; surf.clipMax = a.clipMax;
+        asSurface = surf.bitDepth != X265AMD_DEPTH || surf.layout || a.clipMin >= 0 || a.clipMax >= 0;
         a.ptsIn.push_back(rd<int64_t>(picIn, X265ABI_PIC_pts));
     }
     /* the reconstruction is returned through planes the encoder owns in the reference (pic_out->planes point into its reconstructed picture); here the
@@ -506,7 +533,8 @@ int abi_encoder_encode(void* enc, x265amd_nal** ppNal, uint32_t* piNal, void* pi
         out.planes[0] = recon.data(); out.planes[1] = recon.data() + ysz; out.planes[2] = recon.data() + ysz + csz;
         out.stride[0] = (int32_t)(a.width * isz); out.stride[1] = out.stride[2] = (int32_t)(a.width / 2 * isz);
     }
-    const int ret = x265amd_encoder_encode(a.enc, ppNal, piNal, picIn ? &in : nullptr, picOut ? &out : nullptr);
+    const int ret = asSurface ? x265amd_encoder_encode_surface(a.enc, ppNal, piNal, &surf, 0, picOut ? &out : nullptr)
+                              : x265amd_encoder_encode(a.enc, ppNal, piNal, picIn ? &in : nullptr, picOut ? &out : nullptr);
     if (ret > 0 && picOut)
     {
         for (int k = 0; k < 3; k++) { wr<void*>(picOut, X265ABI_PIC_planes + 8 * k, out.planes[k]); wr<int32_t>(picOut, X265ABI_PIC_stride + 4 * k, out.stride[k]); }
@@ -714,7 +742,49 @@ void abi_csvlog_encode(const void* p, const void* stats, int, int, int argc, cha
     if (rd<uint16_t>(p, X265ABI_PARAM_maxCLL) || rd<uint16_t>(p, X265ABI_PARAM_maxFALL)) fprintf(f, " %-6u, %-6u,", (unsigned)rd<uint16_t>(stats, X265ABI_STATS_maxCLL), (unsigned)rd<uint16_t>(stats, X265ABI_STATS_maxFALL));
     fprintf(f, " %s\n", g_versionStr);
 }
-void abi_dither_image(void*, int, int, int16_t*, int) {}
+/* x265_dither_image (source/encoder/api.cpp:1638-1723): Sierra-2-4A error diffusion of a picture deeper than `bitDepth` down to it, in place, plane by plane.  ditherPlane
+ * (:1640-1678) with its two details: towards 8 bits the samples are PACKED to bytes in place, from the start of every row, while the row stride stays the caller's; and a
+ * picture below 16 bits is first widened to 16 in place over width x height CONSECUTIVE samples of each plane (:1705-1716) -- the reference's loop "assumes width is equal
+ * to stride which happens to be true for file reader outputs", and so does this one.  The caller sets x265_picture.bitDepth afterwards (abrEncApp.cpp:614-618).
+ * errors: width + 1 values.  Nothing happens for pictures of 8 bits or of `bitDepth` bits, as in the reference (which says so on stderr).  X265_CSP_I420 pictures only. */
+void ditherPlane(uint16_t* src, int srcStride, int width, int height, int16_t* errors, int bitDepth)
+{
+    const int lShift = 16 - bitDepth, rShift = 16 - bitDepth + 2, half = 1 << (16 - bitDepth + 1), pixelMax = (1 << bitDepth) - 1;
+    memset(errors, 0, (size_t)(width + 1) * sizeof(int16_t));
+    for (int y = 0; y < height; y++, src += srcStride)
+    {
+        uint8_t* dst8 = (uint8_t*)src;
+        int16_t err = 0;
+        for (int x = 0; x < width; x++)
+        {
+            err = (int16_t)(err * 2 + errors[x] + errors[x + 1]);
+            int v = ((src[x] << 2) + err + half) >> rShift;
+            v = v < 0 ? 0 : (v > pixelMax ? pixelMax : v);
+            errors[x] = err = (int16_t)(src[x] - (v << lShift));
+            if (bitDepth == 8) dst8[x] = (uint8_t)v;
+            else src[x] = (uint16_t)v;
+        }
+    }
+}
+void abi_dither_image(void* picIn, int picWidth, int picHeight, int16_t* errorBuf, int bitDepth)
+{
+    if (!picIn || !errorBuf || picWidth <= 0 || picHeight <= 0 || bitDepth < 8 || bitDepth > 16) return;
+    const int depth = rd<int32_t>(picIn, X265ABI_PIC_bitDepth), csp = rd<int32_t>(picIn, X265ABI_PIC_colorSpace);
+    if (depth <= 8 || depth > 16 || depth == bitDepth) return;
+    if (csp != X265ABI_CSP_I420) return;
+    for (int i = 0; i < 3; i++)
+    {
+        const int width = picWidth >> (i ? 1 : 0), height = picHeight >> (i ? 1 : 0);          /* x265_cli_csps (x265.h:636-644): the chroma planes of 4:2:0 have half the columns and rows */
+        uint16_t* plane = rd<uint16_t*>(picIn, X265ABI_PIC_planes + 8 * i);
+        if (!plane) return;
+        if (depth < 16)
+        {
+            const uint32_t count = (uint32_t)width * (uint32_t)height;
+            for (uint32_t j = 0; j < count; j++) plane[j] = (uint16_t)(plane[j] << (16 - depth));
+        }
+        ditherPlane(plane, rd<int32_t>(picIn, X265ABI_PIC_stride + 4 * i) / 2, width, height, errorBuf, bitDepth);
+    }
+}
 int abi_fail_analysis(void*, void*, int, uint32_t) { return -1; }
 int abi_fail_parse3(void*, const char*, const char*) { return -1; }
 

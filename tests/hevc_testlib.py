@@ -2889,8 +2889,9 @@ def ctu_recon(c, recon_pic, addr):
     return out
 
 
-def ctu_run_hip(L, me, c):
-    """x265amd_compress_ctu_inter for each listed CTU, each on its own 'coded so far' state; same return shape as ctu_run_ref"""
+def ctu_run_hip(L, me, c, ex=False):
+    """x265amd_compress_ctu_inter (ex: x265amd_compress_ctu_inter_ex with edge = NULL) for each listed CTU, each on its own 'coded so far' state; same return shape as
+    ctu_run_ref"""
     import torch
     isz = c["pics"][0].itemsize
     info = np.array([c["info"]], MVPRED_INFO_DT); si = np.array([c["si"]], SLICE_INFO_DT)
@@ -2909,9 +2910,10 @@ def ctu_run_hip(L, me, c):
         ctx = np.zeros(160, np.uint8); ctx[:len(c["starts"][k][0])] = c["starts"][k][0]
         coeff = np.zeros(RD_TILE, np.int16); res = np.zeros(1, CTU_RESULT_DT)
         with call_stream(L) as st_:
-            rc = L.lib.x265amd_compress_ctu_inter(me.ctx, st_, _ptr(info), _ptr(sp), _ptr(si), _ptr(c["ap"]), _ptr(u), _ptr(m), _ptr(c["col"]), _ptr(c["ref_depth"]),
-                                                  _ptr(c["ref_qp0"]), _ptr(planes), len(c["pics"]), C.c_int64(c["stride"]), C.c_int64(c["cstride"]), _ptr(st), a, _ptr(ctx),
-                                                  C.c_uint64(c["starts"][k][1]), _ptr(coeff), _ptr(res))
+            fn = L.lib.x265amd_compress_ctu_inter_ex if ex else L.lib.x265amd_compress_ctu_inter
+            rc = fn(me.ctx, st_, _ptr(info), _ptr(sp), _ptr(si), _ptr(c["ap"]), _ptr(u), _ptr(m), _ptr(c["col"]), _ptr(c["ref_depth"]), _ptr(c["ref_qp0"]), _ptr(planes),
+                    len(c["pics"]), C.c_int64(c["stride"]), C.c_int64(c["cstride"]), _ptr(st), a, _ptr(ctx), C.c_uint64(c["starts"][k][1]), _ptr(coeff), _ptr(res),
+                    *([None] if ex else []))
         assert rc == 0, L.lib.x265amd_last_error()
         cx, cy = (a % ctuW) * 16, (a // ctuW) * 16
         recon_pic = d_pics[-2].cpu().numpy().view(c["pics"][0].dtype)

@@ -1,6 +1,7 @@
 """CTU mode decision of inter slices (x265amd_compress_ctu_inter) against golden results of the reference's own
 Analysis::compressCTU run on CUData / Slice / Frame / MotionReference fixtures of the same pictures and maps
 (tests/golden/ctu_analysis_golden.npz, generated here from oracle/_ref by tests/golden/make_golden.py)."""
+import ctypes as C
 import os
 
 import numpy as np
@@ -70,3 +71,44 @@ def test_hip_compress_ctu_inter_matches_reference_golden():
                     bad = np.argwhere(np.asarray(a) != want)[:6].tolist()
                     raise AssertionError("case %d CTU %d (addr %d): %s differs from the reference's result at %s: got %s want %s" % (
                         k, i, c["ctus"][i], name, bad, np.asarray(a)[tuple(np.array(bad).T)].tolist(), want[tuple(np.array(bad).T)].tolist()))
+
+
+def one_ctu_case():
+    """the first CTU of case 0 (8-bit B slice, early skip, rskip 1): the smallest case of the golden file"""
+    c = make_case(0)
+    assert int(c["ap"]["rskip"][0]) == 1
+    for name in ("ctus", "maps", "starts"):
+        c[name] = c[name][:1]
+    return c
+
+
+@pytest.mark.gpu
+def test_ex_entry_point_without_edge_counts_is_the_plain_one():
+    """x265amd_compress_ctu_inter_ex with edge = NULL and x265amd_compress_ctu_inter are the same call: the same x265amd_ctu_result, units, motion and levels, and those
+    of the reference (the golden file's)."""
+    gold = np.load(GOLD_PATH)
+    c = one_ctu_case()
+    me = T.HipME(8)
+    plain, ex = (T.ctu_pack(T.ctu_run_hip(T.load_hip(8), me, c, ex=e))[0] for e in (False, True))
+    for name in ("res", "ctx", "units", "first", "motion", "coeff"):
+        assert np.array_equal(ex[name], plain[name]), name
+        assert np.array_equal(plain[name], gold["0/0/%s" % name]), name
+
+
+def test_rskip_2_without_edge_counts_is_refused():
+    """A->rskip = 2 with edge = NULL: X265AMD_EINVAL from both entry points.  The configuration is checked before anything touches the device, so no GPU is needed --
+    the motion search context and the plane table are never read (stand-ins here)."""
+    c = one_ctu_case()
+    L = T.load_hip(8)
+    ap = c["ap"].copy()
+    ap["rskip"] = 2
+    info = np.array([c["info"]], T.MVPRED_INFO_DT); si = np.array([c["si"]], T.SLICE_INFO_DT); sp = np.zeros(1, T.INTER_SP_DT)
+    u, m, st = (a.copy() for a in c["maps"][0])
+    me = np.zeros(64, np.uint8); planes = np.zeros(3 * len(c["pics"]), np.uint64); ctx = np.zeros(160, np.uint8)
+    coeff = np.zeros(T.RD_TILE, np.int16); res = np.zeros(1, T.CTU_RESULT_DT)
+    args = [T._ptr(me), None, T._ptr(info), T._ptr(sp), T._ptr(si), T._ptr(ap), T._ptr(u), T._ptr(m), T._ptr(c["col"]), T._ptr(c["ref_depth"]), T._ptr(c["ref_qp0"]),
+            T._ptr(planes), len(c["pics"]), C.c_int64(c["stride"]), C.c_int64(c["cstride"]), T._ptr(st), c["ctus"][0], T._ptr(ctx), C.c_uint64(0), T._ptr(coeff), T._ptr(res)]
+    assert L.lib.x265amd_compress_ctu_inter(*args) == -1            # X265AMD_EINVAL
+    assert L.lib.x265amd_compress_ctu_inter_ex(*args, None) == -1
+    L.lib.x265amd_last_error.restype = C.c_char_p
+    assert b"rskip 2 with the picture's edge counts" in L.lib.x265amd_last_error()

@@ -15,6 +15,9 @@
  *
  * I slices take compressIntraCU (:514-668): checkIntra 2Nx2N (+ NxN at 8x8) through x265amd_check_intra, then the four sub-CUs.
  *
+ * The recursion and everything it calls per CU stay in this one translation unit.  The frame loop around xa_compress_ctu is frame_analysis.hip; the guards of the
+ * reference reads and the motion fields' device mirrors are motion_map.hip; the picture comes in as one record (x265amd_host.h: XaAnalysisArgs).
+ *
  * Scope of this entry point: I, P and B slices (intra candidates through x265amd_intra_in_inter; --b-intra on / off), 2Nx2N, rectangular
  * (--rect) and asymmetric (--amp) partitions with --limit-modes, --limit-refs 0-3, no delta QP (aq-mode 0, no cutree), rd 3-4, rskip 0/1 (2 with the picture's edge counts), early skip on/off.
  */
@@ -30,129 +33,30 @@
 
 using namespace xa_inter;
 
-#include <atomic>
-#include <chrono>
-#include <condition_variable>
 #include <functional>
 #include "xa_fiber.h"
-#include <mutex>
-#include <thread>
-/* X265AMD_TIMING=1: wall time per analysis stage, printed per frame by x265amd_analyse_frame */
-static double g_stageMs[8];
-static const char* const g_stageName[8] = { "merge", "search", "rdInter", "rdIntra", "bidir", "copies", "intraSlice", "other" };
-static bool g_timing = xa_env_present("X265AMD_TIMING");
-static std::atomic<uint64_t> g_aheadStat[4];      /* X265AMD_TIMING: searches started ahead of a leaf's merge check, searches collected, started behind the merge check of a CU with sub-CUs, results the sub-CUs' restriction ruled out */
-static std::atomic<uint64_t> g_chainStat[4], g_chainTicks[8], g_cuStat[2][4][4];      /* [B / P][depth][skipped on the device, merge check on the host, search, intra try] */     /* X265AMD_TIMING: skip chains run, CUs they skipped, stops (not a skip / vector beyond what is published); the device's stage clock */
-struct StageTimer
-{
-    int k; std::chrono::steady_clock::time_point t0;
-    explicit StageTimer(int k_) : k(k_) { if (g_timing) t0 = std::chrono::steady_clock::now(); }
-    ~StageTimer() { if (g_timing) g_stageMs[k] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
-};
+#include "xa_timing.h"
+#include "motion_map.h"
 
-/* ---- reference-picture guards (x265amd_host.h): the row task's hooks live in its task slot ---- */
-static int xa_ref_guard_wait(int pic, int yMin, int yMax, int xMax)
+/* X265AMD_TIMING=1 (xa_timing.h): printed per frame by xa_analyse_frame */
+void xa_timing_report()
 {
-    void** slot = xa_task_slot();
-    const XaRowHooks* h = slot ? (const XaRowHooks*)*slot : nullptr;
-    if (!h || !h->ref_wait) return 0;
-    return h->ref_wait(h->ctx, pic, yMin, yMax, xMax);
-}
-int xa_ref_guard_mc(const x265amd_mc_job* jobs, int n)
-{
-    void** slot = xa_task_slot();
-    if (!slot || !*slot) return 0;
-    int yMin[32], yMax[32], xMax[32];
-    for (int k = 0; k < 32; k++) { yMin[k] = 1 << 30; yMax[k] = -(1 << 30); xMax[k] = -(1 << 30); }
-    for (int i = 0; i < n; i++)
-    {
-        const x265amd_mc_job& j = jobs[i];
-        const int refs[2] = { j.ref0, j.ref1 };
-        const int16_t* mv[2] = { j.mv0, j.mv1 };
-        for (int l = 0; l < 2; l++)
-        {
-            if (refs[l] < 0 || refs[l] >= 32) continue;
-            /* the block moved by the vector's full-sample part (floor) with the taps of the 8-tap luma filter around it (chroma reaches no further in luma terms) */
-            const int y0 = j.y + (mv[l][1] >> 2) - 4, y1 = j.y + j.h - 1 + (mv[l][1] >> 2) + 5, x1 = j.x + j.w - 1 + (mv[l][0] >> 2) + 5;
-            if (y0 < yMin[refs[l]]) yMin[refs[l]] = y0;
-            if (y1 > yMax[refs[l]]) yMax[refs[l]] = y1;
-            if (x1 > xMax[refs[l]]) xMax[refs[l]] = x1;
-        }
-    }
-    for (int k = 0; k < 32; k++) if (yMax[k] > -(1 << 30)) if (xa_ref_guard_wait(k, yMin[k], yMax[k], xMax[k])) return -1;
-    return 0;
-}
-int xa_ref_guard_me(const x265amd_me_job* jobs, const int* pics, int n)
-{
-    void** slot = xa_task_slot();
-    if (!slot || !*slot) return 0;
-    for (int i = 0; i < n; i++)
-    {
-        const x265amd_me_job& j = jobs[i];
-        /* the search area with the interpolation margins and what the pattern / sub-sample refinement may step outside (x265amd_me_plan's bounds) */
-        if (xa_ref_guard_wait(pics[i], j.y + j.mvmin[1] - 8, j.y + j.h + j.mvmax[1] + 8, j.x + j.w + j.mvmax[0] + 10)) return -1;
-    }
-    return 0;
-}
-
-/* ---- device-resident motion maps (inter_chain_dev.h): a host motion field (x265amd_mv_unit array) may have a mirror in device memory the host writes through the BAR;
- * the encoder object registers one per picture, frame-level callers without one get a temporary mirror (xa_analyse_frame) ---- */
-namespace {
-/* blocks are never given back to the runtime while the process lives (hipFree waits for the device, and the job server's kernel is resident): an entry
- * without a host field is a free block of `units` units */
-struct DevMapEntry { std::atomic<const void*> host{ nullptr }; void* dev = nullptr; size_t units = 0; };
-DevMapEntry g_devMaps[512];
-std::mutex g_devMapM;
-}
-void* xa_devmap_register(const x265amd_mv_unit* host, size_t units)
-{
-    if (!host || !units || !xa_queues_enabled()) return nullptr;
-    std::lock_guard<std::mutex> g(g_devMapM);
-    DevMapEntry* blank = nullptr;
-    for (DevMapEntry& e : g_devMaps)
-    {
-        if (e.host.load(std::memory_order_relaxed)) continue;
-        if (e.dev && e.units == units) { e.host.store(host, std::memory_order_release); return e.dev; }
-        if (!e.dev && !blank) blank = &e;
-    }
-    if (!blank) return nullptr;
-    void* d = nullptr;
-    if (hipExtMallocWithFlags(&d, units * sizeof(XaMapUnit), hipDeviceMallocUncached) != hipSuccess) return nullptr;
-    blank->dev = d; blank->units = units;
-    blank->host.store(host, std::memory_order_release);
-    return d;
-}
-void xa_devmap_unregister(const x265amd_mv_unit* host)
-{
-    if (!host) return;
-    std::lock_guard<std::mutex> g(g_devMapM);
-    for (DevMapEntry& e : g_devMaps)
-        if (e.host.load(std::memory_order_relaxed) == host) { e.host.store(nullptr, std::memory_order_release); return; }
-}
-void* xa_devmap_find(const x265amd_mv_unit* host)
-{
-    if (!host) return nullptr;
-    for (DevMapEntry& e : g_devMaps) if (e.host.load(std::memory_order_acquire) == host) return e.dev;
-    return nullptr;
-}
-static inline void devmap_store(XaMapUnit* d, const x265amd_mv_unit& v, int depth)
-{
-    union { XaMapUnit u; uint64_t w[2]; } t;
-    t.w[0] = t.w[1] = 0;
-    t.u.pred_mode = v.pred_mode; t.u.inter_dir = v.inter_dir; t.u.ref_idx[0] = v.ref_idx[0]; t.u.ref_idx[1] = v.ref_idx[1];
-    t.u.mv[0][0] = v.mv[0][0]; t.u.mv[0][1] = v.mv[0][1]; t.u.mv[1][0] = v.mv[1][0]; t.u.mv[1][1] = v.mv[1][1]; t.u.depth = (uint8_t)depth;
-    volatile uint64_t* q = reinterpret_cast<volatile uint64_t*>(d);
-    q[0] = t.w[0]; q[1] = t.w[1];
-}
-/* rows [y4a, y4b) of a host field into its mirror (a picture whose rows arrive from another process: x265amd_encoder_import_row) */
-void xa_devmap_push_rows(const x265amd_mv_unit* host, const x265amd_cu_unit* units, int w4, int y4a, int y4b)
-{
-    XaMapUnit* d = (XaMapUnit*)xa_devmap_find(host);
-    if (!d) return;
-    for (int i = y4a * w4; i < y4b * w4; i++) devmap_store(d + i, host[i], units ? units[i].depth : 0);
-    /* the mirror is written through the write-combining BAR mapping and the caller publishes the rows to OTHER threads next (a release fence drains nothing on
-     * x86): the units must have left this core's buffers before a row task on another core can queue a command that reads them */
-    _mm_sfence();
+    static const char* const stageName[8] = { "merge", "search", "rdInter", "rdIntra", "bidir", "copies", "intraSlice", "other" };
+    fprintf(stderr, "x265amd: skip chains so far: %llu commands, %llu CUs skipped on the device, stopped %llu times at a CU that is not skipped and %llu times at a vector beyond what is published; "
+            "device ms: candidates %.1f, predictions + SA8D %.1f, choice %.1f, transform units %.1f, rate-distortion %.1f, placing %.1f, coder state %.1f (%llu CUs)\n", (unsigned long long)g_chainStat[0].load(),
+            (unsigned long long)g_chainStat[1].load(), (unsigned long long)g_chainStat[2].load(), (unsigned long long)g_chainStat[3].load(), g_chainTicks[0].load() / 1e5, g_chainTicks[1].load() / 1e5,
+            g_chainTicks[2].load() / 1e5, g_chainTicks[3].load() / 1e5, g_chainTicks[4].load() / 1e5, g_chainTicks[5].load() / 1e5, g_chainTicks[7].load() / 1e5, (unsigned long long)g_chainTicks[6].load());
+    fprintf(stderr, "x265amd: searches started ahead so far: %llu beside a leaf's merge check, %llu behind the merge check of a CU with sub-CUs; collected %llu, ruled out by the sub-CUs' reference pictures %llu\n",
+            (unsigned long long)g_aheadStat[0].load(), (unsigned long long)g_aheadStat[2].load(), (unsigned long long)g_aheadStat[1].load(), (unsigned long long)g_aheadStat[3].load());
+    for (int t = 0; t < 2; t++)
+        fprintf(stderr, "x265amd: CUs of %s pictures so far by depth 0..3 (skipped on the device / merge check on the host / searched / intra try): %llu/%llu/%llu/%llu %llu/%llu/%llu/%llu %llu/%llu/%llu/%llu %llu/%llu/%llu/%llu\n",
+                t ? "P" : "B", (unsigned long long)g_cuStat[t][0][0].load(), (unsigned long long)g_cuStat[t][0][1].load(), (unsigned long long)g_cuStat[t][0][2].load(), (unsigned long long)g_cuStat[t][0][3].load(),
+                (unsigned long long)g_cuStat[t][1][0].load(), (unsigned long long)g_cuStat[t][1][1].load(), (unsigned long long)g_cuStat[t][1][2].load(), (unsigned long long)g_cuStat[t][1][3].load(),
+                (unsigned long long)g_cuStat[t][2][0].load(), (unsigned long long)g_cuStat[t][2][1].load(), (unsigned long long)g_cuStat[t][2][2].load(), (unsigned long long)g_cuStat[t][2][3].load(),
+                (unsigned long long)g_cuStat[t][3][0].load(), (unsigned long long)g_cuStat[t][3][1].load(), (unsigned long long)g_cuStat[t][3][2].load(), (unsigned long long)g_cuStat[t][3][3].load());
+    fprintf(stderr, "x265amd: analysis stages (ms):");
+    for (int k = 0; k < 5; k++) { fprintf(stderr, " %s %.1f", stageName[k], g_stageMs[k]); g_stageMs[k] = 0; }
+    fprintf(stderr, "\n");
 }
 
 namespace {
@@ -166,7 +70,8 @@ typedef uint64_t sse_t;
 enum { PRED_MERGE, PRED_SKIP, PRED_2Nx2N, PRED_BIDIR, PRED_INTRA, PRED_INTRA_NxN, PRED_2NxN, PRED_Nx2N, PRED_2NxnU, PRED_2NxnD, PRED_nLx2N, PRED_nRx2N, PRED_SPLIT, NUM_PRED };
 struct SplitData { uint32_t splitRefs, mvCost[2]; uint64_t sa8dCost; };
 const uint64_t kMaxCost = 0x7FFFFFFFFFFFFFFFULL;
-const int kTileElems = 4096 + 2048;
+const uint8_t kChromaScale[58] = { 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23, 24, 25, 26, 27, 28, 29, 29, 30, 31,
+                                  32, 33, 33, 34, 34, 35, 35, 36, 36, 37, 37, 38, 39, 40, 41, 42, 43, 44, 45, 46, 47, 48, 49, 50, 51 };       /* g_chromaScale (4:2:0): the chroma QP of a luma QP */
 
 struct Snap { uint8_t ctx[X265AMD_CTX_STRIDE]; uint64_t frac; };
 
@@ -222,7 +127,7 @@ struct Analyzer
     /* ---- delta QP (pps.bUseDQP): `qp` above is the QP in force -- what Search::setLambdaFromQP was last called with (search.cpp:177-187): the lambdas, the quantiser and the
      * motion costs follow it.  A CU's own QP is the value in force when compress() is entered: set by its parent for a CU at the quantisation groups' depth or above, inherited
      * from its group below that. ---- */
-    const int8_t* cuQp = nullptr;           /* this CTU's group QPs (xa_analyse_frame's cu_qp): [0] the 64x64 CU, [1 + q] its 32x32 CUs */
+    const int8_t* cuQp = nullptr;           /* this CTU's group QPs (XaAnalysisArgs::cu_qp): [0] the 64x64 CU, [1 + q] its 32x32 CUs */
     int ctuQp = 0;                          /* CUData::m_qp[0] of the CTU as compressCTU sets it (topSkipMinDepth's currentQP) */
     x265amd_cabac* qpCoder = nullptr;       /* a bit-counting coder on the picture map: getRefQP and the price of cu_qp_delta (checkDQPForSplitPred) */
     int lambdaQp = 0;                       /* the QP setLambdaFromQP was given (up to 69): the lambdas' and the motion costs'; `qp` is the quantiser's and the coded one, clipped to 51 */
@@ -293,14 +198,17 @@ struct Analyzer
         if (!si->use_dqp || depth + 1 > si->max_cu_dqp_depth) return 0;
         return setLambdaFromQP(cuQp[1 + q]);          /* (max_cu_dqp_depth 1: the children of the CTU) */
     }
+    int openQpCoder()
+    {
+        if (qpCoder) return 0;
+        if (!(qpCoder = x265amd_cabac_open(si, units, 1))) return fail("delta QP: coder");
+        qpCoder->ctuInProgress = true;          /* the analysis of a CTU asks (cabac_coder.h: lastQP) */
+        return 0;
+    }
     /* the price of cu_qp_delta for the mode's first unit (Entropy::codeDeltaQP(cu, 0) in bit-counting mode: mode.contexts.resetBits(); codeDeltaQP; getNumberOfWrittenBits) */
     int addDeltaQpBits(Mode& m, int x, int y)
     {
-        if (!qpCoder)
-        {
-            if (!(qpCoder = x265amd_cabac_open(si, units, 1))) return fail("delta QP: coder");
-            qpCoder->ctuInProgress = true;          /* the analysis of a CTU asks (cabac_coder.h: lastQP) */
-        }
+        if (openQpCoder()) return err;
         if (A->rd_level >= 3)
         {
             x265amd_cu_unit& at = units[(y >> 2) * w4 + (x >> 2)];
@@ -324,11 +232,7 @@ struct Analyzer
     {
         if (!si->use_dqp || depth > si->max_cu_dqp_depth) return 0;
         if (m.u[0].cbf[0] || m.u[0].cbf[1] || m.u[0].cbf[2]) return addDeltaQpBits(m, x, y);
-        if (!qpCoder)
-        {
-            if (!(qpCoder = x265amd_cabac_open(si, units, 1))) return fail("delta QP: coder");
-            qpCoder->ctuInProgress = true;
-        }
+        if (openQpCoder()) return err;
         const int8_t refQp = (int8_t)qpCoder->refQP(x, y);
         const int n4 = 16 >> depth;
         for (int i = 0; i < n4 * n4; i++) m.u[i].qp = refQp;
@@ -340,11 +244,7 @@ struct Analyzer
     int checkDQPForSplitPred(Mode& m, int x, int y, int depth)
     {
         if (!si->use_dqp || depth != si->max_cu_dqp_depth) return 0;
-        if (!qpCoder)
-        {
-            if (!(qpCoder = x265amd_cabac_open(si, units, 1))) return fail("delta QP: coder");
-            qpCoder->ctuInProgress = true;
-        }
+        if (openQpCoder()) return err;
         const int n4 = 16 >> depth;
         bool hasResidual = false;
         for (int i = 0; i < n4 * n4 && !hasResidual; i++) hasResidual = m.u[i].cbf[0] || m.u[i].cbf[1] || m.u[i].cbf[2];
@@ -450,11 +350,9 @@ struct Analyzer
         J.frame_parallel = S->frame_parallel; J.search_range = S->search_range; J.chroma_sa8d = A->rd_level >= 3; J.slice_type = si->slice_type;
         {
             /* Quant::setQPforQuant (quant.cpp:221-244), chroma QP offsets 0: as make_plan (inter_rd.hip) */
-            static const uint8_t chromaScale[58] = { 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23, 24, 25, 26, 27, 28, 29, 29, 30, 31,
-                                                     32, 33, 33, 34, 34, 35, 35, 36, 36, 37, 37, 38, 39, 40, 41, 42, 43, 44, 45, 46, 47, 48, 49, 50, 51 };
             const int qpQuant = qp < 0 ? 0 : (qp > 51 ? 51 : qp), bd = 6 * (X265AMD_DEPTH - 8);
             int qpC = qpQuant < -bd ? -bd : (qpQuant > 57 ? 57 : qpQuant);
-            if (qpC >= 30) qpC = chromaScale[qpC];
+            if (qpC >= 30) qpC = kChromaScale[qpC];
             J.qp_luma = qpQuant + bd; J.qp_chroma = qpC + bd;
         }
         J.tu_log2_max = si->tu_log2_max;
@@ -473,25 +371,19 @@ struct Analyzer
         memcpy(J.anc_flags, chain.usedFlags, 4);
         if (si->use_dqp)
         {
-            if (!qpCoder)
-            {
-                if (!(qpCoder = x265amd_cabac_open(si, units, 1))) return fail("delta QP: coder");
-                qpCoder->ctuInProgress = true;
-            }
+            if (openQpCoder()) return err;
             J.use_dqp = 1; J.max_dqp_depth = si->max_cu_dqp_depth;
             J.prev_qp = qpCoder->lastQP(ctuX, ctuY);
-            static const uint8_t chromaScale[58] = { 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23, 24, 25, 26, 27, 28, 29, 29, 30, 31,
-                                                     32, 33, 33, 34, 34, 35, 35, 36, 36, 37, 37, 38, 39, 40, 41, 42, 43, 44, 45, 46, 47, 48, 49, 50, 51 };
             const int bd = 6 * (X265AMD_DEPTH - 8);
             for (int k = 0; k < (si->max_cu_dqp_depth ? 5 : 1); k++)
             {
                 XaChainJob::QpSet& q = J.qps[k];
-                const int qv = cuQp[k];              /* (not above 51 on a CTU the chain runs on: compress_ctu_impl) */
+                const int qv = cuQp[k];              /* (not above 51 on a CTU the chain runs on: xa_compress_ctu) */
                 uint64_t rd[6];
                 x265amd_rdcost(qv, si->slice_type, A->psy_rd, 0, 0, 0, rd);
                 q.lambda2 = rd[0]; q.lambda = rd[1]; q.psy_rd = (uint32_t)rd[2]; q.qp = qv;
                 int qpC = qv < -bd ? -bd : (qv > 57 ? 57 : qv);
-                if (qpC >= 30) qpC = chromaScale[qpC];
+                if (qpC >= 30) qpC = kChromaScale[qpC];
                 q.qp_luma = qv + bd; q.qp_chroma = qpC + bd;
             }
             J.last_src[0] = -1;
@@ -883,6 +775,31 @@ struct Analyzer
             }
     }
 
+    /* CUData::copyPartFrom + Mode::addSubCosts: the finished sub-CU q of the CU at `depth` into that CU's split mode -- units, motion, costs, levels and, with copyRecon,
+     * its reconstruction (the coder state goes on with the caller) */
+    void gatherSubCU(Mode& split, const Mode& nb, int q, int depth, bool copyRecon)
+    {
+        const int n4 = 16 >> depth, h4n = n4 >> 1, half = 32 >> depth;
+        for (int yy = 0; yy < h4n; yy++)
+            for (int xx = 0; xx < h4n; xx++)
+            {
+                split.u[((q >> 1) * h4n + yy) * n4 + (q & 1) * h4n + xx] = nb.u[yy * h4n + xx];
+                split.m[((q >> 1) * h4n + yy) * n4 + (q & 1) * h4n + xx] = nb.m[yy * h4n + xx];
+            }
+        split.addSubCosts(nb);
+        if (copyRecon) copyTile(split.reconTile, nb.reconTile, (q & 1) * half, (q >> 1) * half, half);
+        const int nc = half * half;
+        memcpy(&split.coeff[(size_t)q * nc], nb.coeff.data(), sizeof(int16_t) * nc);
+        memcpy(&split.coeff[4096 + (size_t)q * nc / 4], nb.coeff.data() + 4096, sizeof(int16_t) * nc / 4);
+        memcpy(&split.coeff[5120 + (size_t)q * nc / 4], nb.coeff.data() + 5120, sizeof(int16_t) * nc / 4);
+    }
+    void setEmptyPart(Mode& split, int q, int depth)        /* CUData::setEmptyPart: sub-CU q lies outside the picture */
+    {
+        const int n4 = 16 >> depth, h4n = n4 >> 1;
+        for (int yy = 0; yy < h4n; yy++)
+            for (int xx = 0; xx < h4n; xx++) split.u[((q >> 1) * h4n + yy) * n4 + (q & 1) * h4n + xx].depth = (uint8_t)(depth + 1);
+    }
+
     /* RD of one candidate through the batch entry points (n = 1) */
     int rdInter(Mode& m, int x, int y, int depth, bool skipOnly)
     {
@@ -1179,11 +1096,9 @@ struct Analyzer
         J.pred_tile = tileAddr(predTile(depth, PRED_2Nx2N)); J.recon_tile = tileAddr(reconTile(depth, PRED_2Nx2N));
         J.lambda = lambda; J.lambda2 = lambda2; J.psy_rd = psyRd;
         {
-            static const uint8_t chromaScale[58] = { 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23, 24, 25, 26, 27, 28, 29, 29, 30, 31,
-                                                     32, 33, 33, 34, 34, 35, 35, 36, 36, 37, 37, 38, 39, 40, 41, 42, 43, 44, 45, 46, 47, 48, 49, 50, 51 };
             const int qpQuant = qp < 0 ? 0 : (qp > 51 ? 51 : qp), bd = 6 * (X265AMD_DEPTH - 8);
             int qpC = qpQuant < -bd ? -bd : (qpQuant > 57 ? 57 : qpQuant);
-            if (qpC >= 30) qpC = chromaScale[qpC];
+            if (qpC >= 30) qpC = kChromaScale[qpC];
             J.qp_luma = qpQuant + bd; J.qp_chroma = qpC + bd;
         }
         J.sign_hide = si->sign_hide != 0; J.chroma_sa8d = A->rd_level >= 3; J.rd_level = A->rd_level; J.do_rd = 1; J.slice_type = si->slice_type;
@@ -1197,11 +1112,7 @@ struct Analyzer
         {
             /* Entropy::codeDeltaQP's value (entropy.cpp:1737-1756): the QP in force against the group's prediction -- which nothing inside the group moves, so it can be
              * taken before the CU's merge check and before its sub-CUs (searchAhead) */
-            if (!qpCoder)
-            {
-                if (!(qpCoder = x265amd_cabac_open(si, units, 1))) return fail("delta QP: coder");
-                qpCoder->ctuInProgress = true;
-            }
+            if (openQpCoder()) return err;
             const int bd = 6 * (X265AMD_DEPTH - 8);
             int dqp = qp - qpCoder->refQP(x, y);
             dqp = (dqp + 78 + bd + (bd / 2)) % (52 + bd) - 26 - (bd / 2);
@@ -1568,6 +1479,119 @@ struct Analyzer
     }
 
     /* compressInterCU_rd5_6 (analysis.cpp:1850-2417) without analysis reuse / CTU info / lossless */
+    /* The order in which compressInterCU_rd0_4 and compressInterCU_rd5_6 try the rectangular (amp false) or the asymmetric partitions under --limit-modes: of two
+     * partitions the one whose sub-CUs' motion costs less goes first, and each is tried only while the sub-CUs' cost stays below the best cost so far plus that
+     * motion cost.  bestCost() is read again at every comparison (a tried partition may have changed it); tryPart(part, slot, refMask0, refMask1) tries one. */
+    template <class Cost, class Try>
+    int tryPartitions(const SplitData splitData[4], uint32_t allSplitRefs, bool amp, bool bHor, bool bVer, Cost bestCost, Try tryPart)
+    {
+        const bool isP = !I->is_inter_b;
+        auto thr = [&](int a, int b) { return isP ? splitData[a].mvCost[0] + splitData[b].mvCost[0]
+                                                  : (splitData[a].mvCost[0] + splitData[b].mvCost[0] + splitData[a].mvCost[1] + splitData[b].mvCost[1] + 1) >> 1; };
+        const uint64_t splitCost = splitData[0].sa8dCost + splitData[1].sa8dCost + splitData[2].sa8dCost + splitData[3].sa8dCost;
+        const uint32_t top = splitData[0].splitRefs | splitData[1].splitRefs, bot = splitData[2].splitRefs | splitData[3].splitRefs;
+        const uint32_t lft = splitData[0].splitRefs | splitData[2].splitRefs, rgt = splitData[1].splitRefs | splitData[3].splitRefs;
+        struct Part { int part, slot; uint32_t m0, m1, thr; };
+        auto pair = [&](const Part& a, const Part& b) -> int {          /* b, a when b's threshold is the smaller one; else a, b */
+            const bool bFirst = b.thr < a.thr;
+            if (bFirst && splitCost < bestCost() + b.thr && tryPart(b.part, b.slot, b.m0, b.m1)) return err;
+            if (splitCost < bestCost() + a.thr && tryPart(a.part, a.slot, a.m0, a.m1)) return err;
+            if (!bFirst && splitCost < bestCost() + b.thr && tryPart(b.part, b.slot, b.m0, b.m1)) return err;
+            return 0;
+        };
+        if (!amp) return pair({ 2, PRED_Nx2N, lft, rgt, thr(0, 2) }, { 1, PRED_2NxN, top, bot, thr(0, 1) });
+        if (bHor && pair({ 4, PRED_2NxnU, top, allSplitRefs, thr(0, 1) }, { 5, PRED_2NxnD, allSplitRefs, bot, thr(2, 3) })) return err;
+        if (bVer && pair({ 6, PRED_nLx2N, lft, allSplitRefs, thr(0, 2) }, { 7, PRED_nRx2N, allSplitRefs, rgt, thr(1, 3) })) return err;
+        return 0;
+    }
+
+    /* ---- X265AMD_CHAIN_VERIFY=2 (debugging): the host repeats what the device decided for the CU and fails on a difference ---- */
+    /* the host's own merge check of the CU the device skipped must arrive at the same mode, cost and coder state */
+    int verifySkip(int x, int y, int depth)
+    {
+        ModeDepth& d = md[depth];
+        const uint64_t devCost = d.best->rdCost; const Snap devCtx = d.best->contexts; const int devCand = d.best->u[0].mvp_idx[0];
+        d.best = nullptr;
+        if (checkMerge(x, y, depth)) return err;
+        if (!d.best || !d.best->isSkipped() || d.best->rdCost != devCost || d.best->u[0].mvp_idx[0] != devCand || d.best->contexts.frac != devCtx.frac ||
+            memcmp(d.best->contexts.ctx, devCtx.ctx, X265AMD_CTX_COUNT))
+        {
+            fprintf(stderr, "x265amd chain verify: poc %d CU (%d,%d) size %d: device skip (candidate %d, cost %llu); host %s candidate %d cost %llu\n", I->poc, x, y, 64 >> depth, devCand,
+                    (unsigned long long)devCost, !d.best ? "nothing" : (d.best->isSkipped() ? "skip" : "merge with residual"), d.best ? d.best->u[0].mvp_idx[0] : -1,
+                    (unsigned long long)(d.best ? d.best->rdCost : 0));
+            return fail("chain verify: the device skipped a CU the host does not skip the same way");
+        }
+        return 0;
+    }
+    /* the host's own merge check must leave the same two modes as the device's (chainMerge) */
+    int verifyMerge(int x, int y, int depth)
+    {
+        ModeDepth& d = md[depth];
+        const uint64_t c0 = d.pred[PRED_SKIP].rdCost, c1 = d.pred[PRED_MERGE].rdCost; const Snap s1 = d.pred[PRED_MERGE].contexts;
+        const uint32_t b1 = d.pred[PRED_MERGE].totalBits, mv1 = d.pred[PRED_MERGE].mvBits; const uint8_t cb[3] = { d.pred[PRED_MERGE].u[0].cbf[0], d.pred[PRED_MERGE].u[0].cbf[1], d.pred[PRED_MERGE].u[0].cbf[2] };
+        const std::vector<int16_t> lv = d.pred[PRED_MERGE].coeff;
+        const bool mergeBest = d.best == &d.pred[PRED_MERGE];
+        d.best = nullptr;
+        if (checkMerge(x, y, depth)) return err;
+        const Mode& hm = d.pred[PRED_MERGE];
+        if (d.pred[PRED_SKIP].rdCost != c0 || hm.rdCost != c1 || hm.totalBits != b1 || hm.mvBits != mv1 || hm.u[0].cbf[0] != cb[0] || hm.u[0].cbf[1] != cb[1] || hm.u[0].cbf[2] != cb[2] ||
+            hm.contexts.frac != s1.frac || memcmp(hm.contexts.ctx, s1.ctx, X265AMD_CTX_COUNT) || hm.coeff != lv || (d.best == &d.pred[PRED_MERGE]) != mergeBest)
+        {
+            fprintf(stderr, "x265amd chain verify: poc %d CU (%d,%d) size %d: merge check differs: skip cost device %llu host %llu, residual mode cost %llu / %llu bits %u / %u mv bits %u / %u "
+                    "cbf %d%d%d / %d%d%d fraction %llu / %llu levels %s best %d / %d\n", I->poc, x, y, 64 >> depth, (unsigned long long)c0, (unsigned long long)d.pred[PRED_SKIP].rdCost,
+                    (unsigned long long)c1, (unsigned long long)hm.rdCost, b1, hm.totalBits, mv1, hm.mvBits, cb[0], cb[1], cb[2], hm.u[0].cbf[0], hm.u[0].cbf[1], hm.u[0].cbf[2],
+                    (unsigned long long)s1.frac, (unsigned long long)hm.contexts.frac, hm.coeff == lv ? "same" : "differ", (int)mergeBest, (int)(d.best == &d.pred[PRED_MERGE]));
+            return fail("chain verify: the device's merge check is not the host's");
+        }
+        return 0;
+    }
+    /* the host's own merge check, candidates and all, must leave the same two modes as the check from the device's candidate (chainMergeFrom) */
+    int verifyMergeFrom(int x, int y, int depth)
+    {
+        ModeDepth& d = md[depth];
+        const uint64_t c0 = d.pred[PRED_SKIP].rdCost, c1 = d.pred[PRED_MERGE].rdCost, s0 = d.pred[PRED_MERGE].sa8dCost; const Snap s1 = d.best->contexts;
+        const int cand0 = d.pred[PRED_MERGE].u[0].mvp_idx[0]; const bool mergeBest = d.best == &d.pred[PRED_MERGE];
+        d.best = nullptr;
+        if (checkMerge(x, y, depth)) return err;
+        if (!d.best || d.pred[PRED_SKIP].rdCost != c0 || d.pred[PRED_MERGE].rdCost != c1 || d.pred[PRED_MERGE].sa8dCost != s0 || d.pred[PRED_MERGE].u[0].mvp_idx[0] != cand0 ||
+            (d.best == &d.pred[PRED_MERGE]) != mergeBest || d.best->contexts.frac != s1.frac || memcmp(d.best->contexts.ctx, s1.ctx, X265AMD_CTX_COUNT))
+        {
+            fprintf(stderr, "x265amd chain verify: poc %d CU (%d,%d) size %d: merge check from the device's candidate %d differs: skip cost %llu / %llu, residual mode %llu / %llu, sa8d cost %llu / %llu, "
+                    "candidate %d, best %d / %d\n", I->poc, x, y, 64 >> depth, cand0, (unsigned long long)c0, (unsigned long long)d.pred[PRED_SKIP].rdCost, (unsigned long long)c1,
+                    (unsigned long long)d.pred[PRED_MERGE].rdCost, (unsigned long long)s0, (unsigned long long)d.pred[PRED_MERGE].sa8dCost, d.pred[PRED_MERGE].u[0].mvp_idx[0], (int)mergeBest,
+                    (int)(d.best == &d.pred[PRED_MERGE]));
+            return fail("chain verify: the merge check from the device's candidate is not the host's");
+        }
+        return 0;
+    }
+    /* the ordinary search and rate-distortion of the CU must give the fused search's mode (checkInterFused); the host's result stays */
+    int verifyFused(int x, int y, int depth, uint32_t allSplitRefs)
+    {
+        ModeDepth& d = md[depth];
+        const int size = 64 >> depth;
+        const Mode fm = d.pred[PRED_2Nx2N];
+        if (checkInter(x, y, depth, allSplitRefs)) return err;
+        Mode& hm = d.pred[PRED_2Nx2N];
+        const uint64_t hs = hm.sa8dCost; const uint32_t hb = hm.sa8dBits;
+        if (rdInter(hm, x, y, depth, false)) return err;
+        if (memcmp(&fm.u[0], &hm.u[0], sizeof(x265amd_cu_unit)) || memcmp(&fm.m[0], &hm.m[0], sizeof(x265amd_mv_unit)) || fm.sa8dCost != hs || fm.sa8dBits != hb ||
+            (fusedRd[depth] && (fm.rdCost != hm.rdCost || fm.totalBits != hm.totalBits || fm.mvBits != hm.mvBits || fm.coeff != hm.coeff || fm.contexts.frac != hm.contexts.frac ||
+                                memcmp(fm.contexts.ctx, hm.contexts.ctx, X265AMD_CTX_COUNT) || fm.psyEnergy != hm.psyEnergy || fm.distortion != hm.distortion)))
+        {
+            fprintf(stderr, "x265amd search verify: poc %d CU (%d,%d) size %d: device ref %d mv (%d,%d) mvd (%d,%d) mvp %d sa8d cost %llu bits %u rd %llu bits %u/%u cbf %d%d%d dist %llu psy %u; "
+                    "host ref %d mv (%d,%d) mvd (%d,%d) mvp %d sa8d cost %llu bits %u rd %llu bits %u/%u cbf %d%d%d dist %llu psy %u levels %s contexts %s\n", I->poc, x, y, size,
+                    fm.u[0].ref_idx[0], fm.m[0].mv[0][0], fm.m[0].mv[0][1], fm.u[0].mvd[0][0], fm.u[0].mvd[0][1], fm.u[0].mvp_idx[0], (unsigned long long)fm.sa8dCost, fm.sa8dBits,
+                    (unsigned long long)fm.rdCost, fm.totalBits, fm.mvBits, fm.u[0].cbf[0], fm.u[0].cbf[1], fm.u[0].cbf[2], (unsigned long long)fm.distortion, fm.psyEnergy,
+                    hm.u[0].ref_idx[0], hm.m[0].mv[0][0], hm.m[0].mv[0][1], hm.u[0].mvd[0][0], hm.u[0].mvd[0][1], hm.u[0].mvp_idx[0], (unsigned long long)hs, hb,
+                    (unsigned long long)hm.rdCost, hm.totalBits, hm.mvBits, hm.u[0].cbf[0], hm.u[0].cbf[1], hm.u[0].cbf[2], (unsigned long long)hm.distortion, hm.psyEnergy,
+                    fm.coeff == hm.coeff ? "same" : "differ", memcmp(fm.contexts.ctx, hm.contexts.ctx, X265AMD_CTX_COUNT) ? "differ" : "same");
+            return fail("search verify: the fused search is not the host's");
+        }
+        hm.sa8dCost = hs; hm.sa8dBits = hb;
+        fusedRd[depth] = true;
+        return 0;
+    }
+
     int compress56(int x, int y, int depth, SplitData& splitOut)
     {
         ModeDepth& d = md[depth];
@@ -1607,7 +1631,7 @@ struct Analyzer
             Mode& split = d.pred[PRED_SPLIT];
             split.initCosts();
             split.predTile = predTile(depth, PRED_SPLIT); split.reconTile = reconTile(depth, PRED_SPLIT);
-            const int n4 = 16 >> depth, half = size >> 1, h4n = n4 >> 1;
+            const int half = size >> 1;
             const Snap* nextContext = &d.cur;
             splitIntra = false;
             for (int q = 0; q < 4; q++)
@@ -1620,23 +1644,10 @@ struct Analyzer
                     if (compress56(cx, cy, depth + 1, splitData[q])) return err;
                     const Mode& nb = *md[depth + 1].best;
                     splitIntra |= nb.u[0].pred_mode == X265AMD_MODE_INTRA;
-                    for (int yy = 0; yy < h4n; yy++)
-                        for (int xx = 0; xx < h4n; xx++)
-                        {
-                            split.u[((q >> 1) * h4n + yy) * n4 + (q & 1) * h4n + xx] = nb.u[yy * h4n + xx];
-                            split.m[((q >> 1) * h4n + yy) * n4 + (q & 1) * h4n + xx] = nb.m[yy * h4n + xx];
-                        }
-                    split.addSubCosts(nb);
-                    copyTile(split.reconTile, nb.reconTile, (q & 1) * half, (q >> 1) * half, half);
-                    const int nc = half * half;
-                    memcpy(&split.coeff[(size_t)q * nc], nb.coeff.data(), sizeof(int16_t) * nc);
-                    memcpy(&split.coeff[4096 + (size_t)q * nc / 4], nb.coeff.data() + 4096, sizeof(int16_t) * nc / 4);
-                    memcpy(&split.coeff[5120 + (size_t)q * nc / 4], nb.coeff.data() + 5120, sizeof(int16_t) * nc / 4);
+                    gatherSubCU(split, nb, q, depth, true);
                     nextContext = &nb.contexts;
                 }
-                else
-                    for (int yy = 0; yy < h4n; yy++)            /* setEmptyPart */
-                        for (int xx = 0; xx < h4n; xx++) split.u[((q >> 1) * h4n + yy) * n4 + (q & 1) * h4n + xx].depth = (uint8_t)(depth + 1);
+                else setEmptyPart(split, q, depth);
             }
             split.contexts = *nextContext;
             if (mightNotSplit) addSplitFlagCost(split, x, y, depth);
@@ -1665,42 +1676,16 @@ struct Analyzer
                         checkBestMode(bidir, depth);
                     }
                 }
-                const bool isP = !I->is_inter_b;
-                auto thr = [&](int a, int b) { return isP ? splitData[a].mvCost[0] + splitData[b].mvCost[0]
-                                                          : (splitData[a].mvCost[0] + splitData[b].mvCost[0] + splitData[a].mvCost[1] + splitData[b].mvCost[1] + 1) >> 1; };
-                const uint64_t splitCost = splitData[0].sa8dCost + splitData[1].sa8dCost + splitData[2].sa8dCost + splitData[3].sa8dCost;
-                const uint32_t top = splitData[0].splitRefs | splitData[1].splitRefs, bot = splitData[2].splitRefs | splitData[3].splitRefs;
-                const uint32_t lft = splitData[0].splitRefs | splitData[2].splitRefs, rgt = splitData[1].splitRefs | splitData[3].splitRefs;
-                if (A->rect)
+                auto bestCost = [&]() { return d.best->rdCost; };
+                if (A->rect && tryPartitions(splitData, allSplitRefs, false, false, false, bestCost, interRd)) return err;
+                if (A->amp && si->max_amp_depth > depth)
                 {
-                    const uint32_t t2NxN = thr(0, 1), tNx2N = thr(0, 2);
-                    const bool first2NxN = t2NxN < tNx2N;
-                    if (first2NxN && splitCost < d.best->rdCost + t2NxN) { if (interRd(1, PRED_2NxN, top, bot)) return err; }
-                    if (splitCost < d.best->rdCost + tNx2N) { if (interRd(2, PRED_Nx2N, lft, rgt)) return err; }
-                    if (!first2NxN && splitCost < d.best->rdCost + t2NxN) { if (interRd(1, PRED_2NxN, top, bot)) return err; }
-                }
-                if ((A->rect || A->amp) && A->amp && si->max_amp_depth > depth)
-                {
-                    const uint32_t tU = thr(0, 1), tD = thr(2, 3), tL = thr(0, 2), tR = thr(1, 3);
                     bool bHor = false, bVer = false;
                     const int bp = d.best->u[0].part_size;
                     if (bp == 1) bHor = true;
                     else if (bp == 2) bVer = true;
                     else if (bp == 0 && !d.best->u[0].merge_flag) { bHor = true; bVer = true; }
-                    if (bHor)
-                    {
-                        const bool firstD = tD < tU;
-                        if (firstD && splitCost < d.best->rdCost + tD) { if (interRd(5, PRED_2NxnD, allSplitRefs, bot)) return err; }
-                        if (splitCost < d.best->rdCost + tU) { if (interRd(4, PRED_2NxnU, top, allSplitRefs)) return err; }
-                        if (!firstD && splitCost < d.best->rdCost + tD) { if (interRd(5, PRED_2NxnD, allSplitRefs, bot)) return err; }
-                    }
-                    if (bVer)
-                    {
-                        const bool firstR = tR < tL;
-                        if (firstR && splitCost < d.best->rdCost + tR) { if (interRd(7, PRED_nRx2N, allSplitRefs, rgt)) return err; }
-                        if (splitCost < d.best->rdCost + tL) { if (interRd(6, PRED_nLx2N, lft, allSplitRefs)) return err; }
-                        if (!firstR && splitCost < d.best->rdCost + tR) { if (interRd(7, PRED_nRx2N, allSplitRefs, rgt)) return err; }
-                    }
+                    if (tryPartitions(splitData, allSplitRefs, true, bHor, bVer, bestCost, interRd)) return err;
                 }
                 if ((!I->is_inter_b || A->b_intra) && log2 != 6 && (!A->limit_refs || splitIntra))
                 {
@@ -1751,7 +1736,6 @@ struct Analyzer
         bool deferred = false, deferredDone = false;
         if ((log2 == 4 || log2 == 5) && mightNotSplit && mightSplit)
         {
-            Mode& m = d.pred[PRED_INTRA];
             x265amd_rd_cu c;
             memset(&c, 0, sizeof(c));
             c.x = (int16_t)x; c.y = (int16_t)y; c.log2_size = (uint8_t)log2; cuQp2(c);
@@ -1772,7 +1756,6 @@ struct Analyzer
             }
             if (b < 0) return err = b;
             deferred = b == 1;
-            (void)m;
         }
         if (log2 != 6 && mightNotSplit && !deferred)
         {
@@ -1885,23 +1868,10 @@ struct Analyzer
                                     (unsigned)nb.lumaDistortion, (unsigned)nb.chromaDistortion, nb.psyEnergy, (unsigned)nb.resEnergy, (unsigned long long)nb.contexts.frac);
                         }
                     }
-                    for (int yy = 0; yy < h4n; yy++)
-                        for (int xx = 0; xx < h4n; xx++)
-                        {
-                            split.u[((q >> 1) * h4n + yy) * n4 + (q & 1) * h4n + xx] = nb.u[yy * h4n + xx];
-                            split.m[((q >> 1) * h4n + yy) * n4 + (q & 1) * h4n + xx] = nb.m[yy * h4n + xx];
-                        }
-                    split.addSubCosts(nb);
-                    copyTile(split.reconTile, nb.reconTile, (q & 1) * half, (q >> 1) * half, half);
-                    const int nc = half * half;
-                    memcpy(&split.coeff[(size_t)q * nc], nb.coeff.data(), sizeof(int16_t) * nc);
-                    memcpy(&split.coeff[4096 + (size_t)q * nc / 4], nb.coeff.data() + 4096, sizeof(int16_t) * nc / 4);
-                    memcpy(&split.coeff[5120 + (size_t)q * nc / 4], nb.coeff.data() + 5120, sizeof(int16_t) * nc / 4);
+                    gatherSubCU(split, nb, q, depth, true);
                     nextContext = &nb.contexts;
                 }
-                else
-                    for (int yy = 0; yy < h4n; yy++)
-                        for (int xx = 0; xx < h4n; xx++) split.u[((q >> 1) * h4n + yy) * n4 + (q & 1) * h4n + xx].depth = (uint8_t)(depth + 1);
+                else setEmptyPart(split, q, depth);
             }
             split.contexts = *nextContext;
             if (mightNotSplit) addSplitFlagCost(split, x, y, depth);
@@ -1946,6 +1916,7 @@ struct Analyzer
         const bool mightNotSplit = x + size <= I->pic_width && y + size <= I->pic_height;
         const uint32_t minDepth = topSkipMinDepth(x, y, depth);
         const int myQp = qp;                    /* the `qp` argument of compressInterCU_rd0_4 */
+        static const bool verify2 = xa_env_int("X265AMD_CHAIN_VERIFY", 0) >= 2;        /* debugging: the verify* methods */
         bool skipModes = false, skipRecursion = false, splitIntra = true;
         SplitData splitData[4];
         memset(splitData, 0, sizeof(splitData));
@@ -1979,67 +1950,16 @@ struct Analyzer
             }
             if (chain.on && chainSkip(node, x, y, depth, devSkip)) return err;
             if (g_timing) g_cuStat[si->slice_type == 1][depth][devSkip ? 0 : 1]++;
-            static const bool verify2 = xa_env_int("X265AMD_CHAIN_VERIFY", 0) >= 2;
-            if (devSkip && verify2)
-            {
-                /* debugging: the host's own merge check of the CU the device skipped must arrive at the same mode, cost and coder state */
-                const uint64_t devCost = d.best->rdCost; const Snap devCtx = d.best->contexts; const int devCand = d.best->u[0].mvp_idx[0];
-                d.best = nullptr;
-                if (checkMerge(x, y, depth)) return err;
-                if (!d.best || !d.best->isSkipped() || d.best->rdCost != devCost || d.best->u[0].mvp_idx[0] != devCand || d.best->contexts.frac != devCtx.frac ||
-                    memcmp(d.best->contexts.ctx, devCtx.ctx, X265AMD_CTX_COUNT))
-                {
-                    fprintf(stderr, "x265amd chain verify: poc %d CU (%d,%d) size %d: device skip (candidate %d, cost %llu); host %s candidate %d cost %llu\n", I->poc, x, y, size, devCand,
-                            (unsigned long long)devCost, !d.best ? "nothing" : (d.best->isSkipped() ? "skip" : "merge with residual"), d.best ? d.best->u[0].mvp_idx[0] : -1,
-                            (unsigned long long)(d.best ? d.best->rdCost : 0));
-                    return fail("chain verify: the device skipped a CU the host does not skip the same way");
-                }
-            }
+            if (devSkip && verify2 && verifySkip(x, y, depth)) return err;
             if (!devSkip)
             {
                 chain.frDirty[depth] = true;            /* this CU is the host's: what the chain decides below it stays inside it */
                 bool devMerge = false;
                 if (chain.on && chainMerge(node, x, y, depth, devMerge)) return err;
-                static const bool verify3 = xa_env_int("X265AMD_CHAIN_VERIFY", 0) >= 2;
-                if (devMerge && verify3)
-                {
-                    /* debugging: the host's own merge check must leave the same two modes */
-                    const uint64_t c0 = d.pred[PRED_SKIP].rdCost, c1 = d.pred[PRED_MERGE].rdCost; const Snap s1 = d.pred[PRED_MERGE].contexts;
-                    const uint32_t b1 = d.pred[PRED_MERGE].totalBits, mv1 = d.pred[PRED_MERGE].mvBits; const uint8_t cb[3] = { d.pred[PRED_MERGE].u[0].cbf[0], d.pred[PRED_MERGE].u[0].cbf[1], d.pred[PRED_MERGE].u[0].cbf[2] };
-                    const std::vector<int16_t> lv = d.pred[PRED_MERGE].coeff;
-                    const bool mergeBest = d.best == &d.pred[PRED_MERGE];
-                    d.best = nullptr;
-                    if (checkMerge(x, y, depth)) return err;
-                    const Mode& hm = d.pred[PRED_MERGE];
-                    if (d.pred[PRED_SKIP].rdCost != c0 || hm.rdCost != c1 || hm.totalBits != b1 || hm.mvBits != mv1 || hm.u[0].cbf[0] != cb[0] || hm.u[0].cbf[1] != cb[1] || hm.u[0].cbf[2] != cb[2] ||
-                        hm.contexts.frac != s1.frac || memcmp(hm.contexts.ctx, s1.ctx, X265AMD_CTX_COUNT) || hm.coeff != lv || (d.best == &d.pred[PRED_MERGE]) != mergeBest)
-                    {
-                        fprintf(stderr, "x265amd chain verify: poc %d CU (%d,%d) size %d: merge check differs: skip cost device %llu host %llu, residual mode cost %llu / %llu bits %u / %u mv bits %u / %u "
-                                "cbf %d%d%d / %d%d%d fraction %llu / %llu levels %s best %d / %d\n", I->poc, x, y, size, (unsigned long long)c0, (unsigned long long)d.pred[PRED_SKIP].rdCost,
-                                (unsigned long long)c1, (unsigned long long)hm.rdCost, b1, hm.totalBits, mv1, hm.mvBits, cb[0], cb[1], cb[2], hm.u[0].cbf[0], hm.u[0].cbf[1], hm.u[0].cbf[2],
-                                (unsigned long long)s1.frac, (unsigned long long)hm.contexts.frac, hm.coeff == lv ? "same" : "differ", (int)mergeBest, (int)(d.best == &d.pred[PRED_MERGE]));
-                        return fail("chain verify: the device's merge check is not the host's");
-                    }
-                }
+                if (devMerge && verify2 && verifyMerge(x, y, depth)) return err;
                 bool devFrom = false;
                 if (!devMerge && chain.on && chainMergeFrom(node, x, y, depth, devFrom)) return err;
-                if (devFrom && verify3)
-                {
-                    /* debugging: the host's own merge check, candidates and all, must leave the same two modes */
-                    const uint64_t c0 = d.pred[PRED_SKIP].rdCost, c1 = d.pred[PRED_MERGE].rdCost, s0 = d.pred[PRED_MERGE].sa8dCost; const Snap s1 = d.best->contexts;
-                    const int cand0 = d.pred[PRED_MERGE].u[0].mvp_idx[0]; const bool mergeBest = d.best == &d.pred[PRED_MERGE];
-                    d.best = nullptr;
-                    if (checkMerge(x, y, depth)) return err;
-                    if (!d.best || d.pred[PRED_SKIP].rdCost != c0 || d.pred[PRED_MERGE].rdCost != c1 || d.pred[PRED_MERGE].sa8dCost != s0 || d.pred[PRED_MERGE].u[0].mvp_idx[0] != cand0 ||
-                        (d.best == &d.pred[PRED_MERGE]) != mergeBest || d.best->contexts.frac != s1.frac || memcmp(d.best->contexts.ctx, s1.ctx, X265AMD_CTX_COUNT))
-                    {
-                        fprintf(stderr, "x265amd chain verify: poc %d CU (%d,%d) size %d: merge check from the device's candidate %d differs: skip cost %llu / %llu, residual mode %llu / %llu, sa8d cost %llu / %llu, "
-                                "candidate %d, best %d / %d\n", I->poc, x, y, size, cand0, (unsigned long long)c0, (unsigned long long)d.pred[PRED_SKIP].rdCost, (unsigned long long)c1,
-                                (unsigned long long)d.pred[PRED_MERGE].rdCost, (unsigned long long)s0, (unsigned long long)d.pred[PRED_MERGE].sa8dCost, d.pred[PRED_MERGE].u[0].mvp_idx[0], (int)mergeBest,
-                                (int)(d.best == &d.pred[PRED_MERGE]));
-                        return fail("chain verify: the merge check from the device's candidate is not the host's");
-                    }
-                }
+                if (devFrom && verify2 && verifyMergeFrom(x, y, depth)) return err;
                 if (!devMerge && !devFrom && checkMerge(x, y, depth)) return err;
             }
             skipModes = A->early_skip && d.best && d.best->isSkipped();
@@ -2075,7 +1995,7 @@ struct Analyzer
             Mode& split = d.pred[PRED_SPLIT];
             split.initCosts();
             split.predTile = predTile(depth, PRED_SPLIT); split.reconTile = reconTile(depth, PRED_SPLIT);
-            const int n4 = 16 >> depth, half = size >> 1, h4n = n4 >> 1;
+            const int half = size >> 1;
             const Snap* nextContext = &d.cur;
             splitIntra = false;
             int childNode = node + 1;                   /* pre-order: the first sub-CU follows its parent, the others follow their elder's subtree */
@@ -2092,23 +2012,10 @@ struct Analyzer
                     if (!childDev) { childrenDev = false; chain.frDirty[depth] = true; }
                     const Mode& nb = *md[depth + 1].best;
                     splitIntra |= nb.u[0].pred_mode == X265AMD_MODE_INTRA;
-                    for (int yy = 0; yy < h4n; yy++)
-                        for (int xx = 0; xx < h4n; xx++)
-                        {
-                            split.u[((q >> 1) * h4n + yy) * n4 + (q & 1) * h4n + xx] = nb.u[yy * h4n + xx];
-                            split.m[((q >> 1) * h4n + yy) * n4 + (q & 1) * h4n + xx] = nb.m[yy * h4n + xx];
-                        }
-                    split.addSubCosts(nb);
-                    if (!childDev) copyTile(split.reconTile, nb.reconTile, (q & 1) * half, (q >> 1) * half, half);     /* the device put its CUs' samples into every enclosing tile itself */
-                    const int nc = half * half;
-                    memcpy(&split.coeff[(size_t)q * nc], nb.coeff.data(), sizeof(int16_t) * nc);
-                    memcpy(&split.coeff[4096 + (size_t)q * nc / 4], nb.coeff.data() + 4096, sizeof(int16_t) * nc / 4);
-                    memcpy(&split.coeff[5120 + (size_t)q * nc / 4], nb.coeff.data() + 5120, sizeof(int16_t) * nc / 4);
+                    gatherSubCU(split, nb, q, depth, !childDev);        /* (the device put its CUs' samples into every enclosing tile itself) */
                     nextContext = &nb.contexts;
                 }
-                else
-                    for (int yy = 0; yy < h4n; yy++)            /* setEmptyPart */
-                        for (int xx = 0; xx < h4n; xx++) split.u[((q >> 1) * h4n + yy) * n4 + (q & 1) * h4n + xx].depth = (uint8_t)(depth + 1);
+                else setEmptyPart(split, q, depth);
             }
             split.contexts = *nextContext;
             if (mightNotSplit) addSplitFlagCost(split, x, y, depth);
@@ -2126,34 +2033,7 @@ struct Analyzer
                 bool fused = false;
                 fusedRd[depth] = false;
                 if (!(A->rect || A->amp) && checkInterFused(x, y, depth, allSplitRefs, fused)) return err;
-                if (fused)
-                {
-                    static const bool verifyS = xa_env_int("X265AMD_CHAIN_VERIFY", 0) >= 2;
-                    if (verifyS)
-                    {
-                        /* debugging: the ordinary search and rate-distortion of the same CU must give the same mode */
-                        const Mode fm = d.pred[PRED_2Nx2N];
-                        if (checkInter(x, y, depth, allSplitRefs)) return err;
-                        Mode& hm = d.pred[PRED_2Nx2N];
-                        const uint64_t hs = hm.sa8dCost; const uint32_t hb = hm.sa8dBits;
-                        if (rdInter(hm, x, y, depth, false)) return err;
-                        if (memcmp(&fm.u[0], &hm.u[0], sizeof(x265amd_cu_unit)) || memcmp(&fm.m[0], &hm.m[0], sizeof(x265amd_mv_unit)) || fm.sa8dCost != hs || fm.sa8dBits != hb ||
-                            (fusedRd[depth] && (fm.rdCost != hm.rdCost || fm.totalBits != hm.totalBits || fm.mvBits != hm.mvBits || fm.coeff != hm.coeff || fm.contexts.frac != hm.contexts.frac ||
-                                                memcmp(fm.contexts.ctx, hm.contexts.ctx, X265AMD_CTX_COUNT) || fm.psyEnergy != hm.psyEnergy || fm.distortion != hm.distortion)))
-                        {
-                            fprintf(stderr, "x265amd search verify: poc %d CU (%d,%d) size %d: device ref %d mv (%d,%d) mvd (%d,%d) mvp %d sa8d cost %llu bits %u rd %llu bits %u/%u cbf %d%d%d dist %llu psy %u; "
-                                    "host ref %d mv (%d,%d) mvd (%d,%d) mvp %d sa8d cost %llu bits %u rd %llu bits %u/%u cbf %d%d%d dist %llu psy %u levels %s contexts %s\n", I->poc, x, y, size,
-                                    fm.u[0].ref_idx[0], fm.m[0].mv[0][0], fm.m[0].mv[0][1], fm.u[0].mvd[0][0], fm.u[0].mvd[0][1], fm.u[0].mvp_idx[0], (unsigned long long)fm.sa8dCost, fm.sa8dBits,
-                                    (unsigned long long)fm.rdCost, fm.totalBits, fm.mvBits, fm.u[0].cbf[0], fm.u[0].cbf[1], fm.u[0].cbf[2], (unsigned long long)fm.distortion, fm.psyEnergy,
-                                    hm.u[0].ref_idx[0], hm.m[0].mv[0][0], hm.m[0].mv[0][1], hm.u[0].mvd[0][0], hm.u[0].mvd[0][1], hm.u[0].mvp_idx[0], (unsigned long long)hs, hb,
-                                    (unsigned long long)hm.rdCost, hm.totalBits, hm.mvBits, hm.u[0].cbf[0], hm.u[0].cbf[1], hm.u[0].cbf[2], (unsigned long long)hm.distortion, hm.psyEnergy,
-                                    fm.coeff == hm.coeff ? "same" : "differ", memcmp(fm.contexts.ctx, hm.contexts.ctx, X265AMD_CTX_COUNT) ? "differ" : "same");
-                            return fail("search verify: the fused search is not the host's");
-                        }
-                        hm.sa8dCost = hs; hm.sa8dBits = hb;
-                        fusedRd[depth] = true;
-                    }
-                }
+                if (fused) { if (verify2 && verifyFused(x, y, depth, allSplitRefs)) return err; }
                 else if (checkInter(x, y, depth, allSplitRefs)) return err;
                 Mode* bestInter = &d.pred[PRED_2Nx2N];
                 if (A->limit_refs & 2)                                                     /* X265_REF_LIMIT_CU */
@@ -2164,49 +2044,22 @@ struct Analyzer
                 Mode& bidir = d.pred[PRED_BIDIR];
                 /* rectangular and asymmetric partitions (analysis.cpp:1447-1594); with limit-modes only where the sub-CUs' motion suggests it */
                 {
-                    const Mode& p2N = d.pred[PRED_2Nx2N];
-                    const bool isP = !I->is_inter_b;
-                    auto thr = [&](int a, int b) { return isP ? splitData[a].mvCost[0] + splitData[b].mvCost[0]
-                                                              : (splitData[a].mvCost[0] + splitData[b].mvCost[0] + splitData[a].mvCost[1] + splitData[b].mvCost[1] + 1) >> 1; };
-                    const uint64_t splitCost = splitData[0].sa8dCost + splitData[1].sa8dCost + splitData[2].sa8dCost + splitData[3].sa8dCost;
+                    auto bestCost = [&]() { return d.pred[PRED_2Nx2N].sa8dCost; };
                     auto tryPart = [&](int part, int slot, uint32_t m0, uint32_t m1) -> int {
                         const uint32_t masks[2] = { m0, m1 };
                         if (checkInterPart(x, y, depth, part, slot, masks)) return err;
                         if (d.pred[slot].sa8dCost < bestInter->sa8dCost) bestInter = &d.pred[slot];
                         return 0;
                     };
-                    const uint32_t top = splitData[0].splitRefs | splitData[1].splitRefs, bot = splitData[2].splitRefs | splitData[3].splitRefs;
-                    const uint32_t lft = splitData[0].splitRefs | splitData[2].splitRefs, rgt = splitData[1].splitRefs | splitData[3].splitRefs;
-                    if (A->rect)
-                    {
-                        const uint32_t t2NxN = thr(0, 1), tNx2N = thr(0, 2);
-                        const bool first2NxN = t2NxN < tNx2N;
-                        if (first2NxN && splitCost < p2N.sa8dCost + t2NxN) { if (tryPart(1, PRED_2NxN, top, bot)) return err; }
-                        if (splitCost < p2N.sa8dCost + tNx2N) { if (tryPart(2, PRED_Nx2N, lft, rgt)) return err; }
-                        if (!first2NxN && splitCost < p2N.sa8dCost + t2NxN) { if (tryPart(1, PRED_2NxN, top, bot)) return err; }
-                    }
+                    if (A->rect && tryPartitions(splitData, allSplitRefs, false, false, false, bestCost, tryPart)) return err;
                     if (A->amp && si->max_amp_depth > depth)
                     {
-                        const uint32_t tU = thr(0, 1), tD = thr(2, 3), tL = thr(0, 2), tR = thr(1, 3);
                         bool bHor = false, bVer = false;
                         const int bp = bestInter->u[0].part_size;
                         if (bp == 1) bHor = true;
                         else if (bp == 2) bVer = true;
                         else if (bp == 0 && d.best && (d.best->u[0].cbf[0] || d.best->u[0].cbf[1] || d.best->u[0].cbf[2])) { bHor = true; bVer = true; }
-                        if (bHor)
-                        {
-                            const bool firstD = tD < tU;
-                            if (firstD && splitCost < p2N.sa8dCost + tD) { if (tryPart(5, PRED_2NxnD, allSplitRefs, bot)) return err; }
-                            if (splitCost < p2N.sa8dCost + tU) { if (tryPart(4, PRED_2NxnU, top, allSplitRefs)) return err; }
-                            if (!firstD && splitCost < p2N.sa8dCost + tD) { if (tryPart(5, PRED_2NxnD, allSplitRefs, bot)) return err; }
-                        }
-                        if (bVer)
-                        {
-                            const bool firstR = tR < tL;
-                            if (firstR && splitCost < p2N.sa8dCost + tR) { if (tryPart(7, PRED_nRx2N, allSplitRefs, rgt)) return err; }
-                            if (splitCost < p2N.sa8dCost + tL) { if (tryPart(6, PRED_nLx2N, lft, allSplitRefs)) return err; }
-                            if (!firstR && splitCost < p2N.sa8dCost + tR) { if (tryPart(7, PRED_nRx2N, allSplitRefs, rgt)) return err; }
-                        }
+                        if (tryPartitions(splitData, allSplitRefs, true, bHor, bVer, bestCost, tryPart)) return err;
                     }
                 }
                 const bool bTryIntra = (!I->is_inter_b || A->b_intra) && log2 != 6;
@@ -2288,36 +2141,32 @@ struct Analyzer
 
 } // namespace
 
-static int compress_ctu_impl(x265amd_me_ctx* me, void* stream, const x265amd_mvpred_info* I, const x265amd_inter_search_params* S,
-                             const x265amd_slice_info* si, const x265amd_analysis_params* A, x265amd_cu_unit* units, x265amd_mv_unit* cur,
-                             const x265amd_mv_unit* col, const uint8_t* ref_depth, const int8_t* ref_qp0, const uint64_t* h_planes, int num_pics,
-                             intptr_t stride, intptr_t cstride, x265amd_cu_stat* cu_stat, int ctu_addr, const uint8_t* ctx_in, uint64_t frac_in,
-                             int16_t* coeff_out, x265amd_ctu_result* out, XaMapUnit* dCur, const XaMapUnit* dCol, const int8_t* cu_qp = nullptr, const XaTuRecs* tu_recs = nullptr,
-                             const x265amd_rskip_edge* edge = nullptr);
-extern "C" int x265amd_compress_ctu_inter(x265amd_me_ctx* me, void* stream, const x265amd_mvpred_info* I, const x265amd_inter_search_params* S,
-                                          const x265amd_slice_info* si, const x265amd_analysis_params* A, x265amd_cu_unit* units, x265amd_mv_unit* cur,
-                                          const x265amd_mv_unit* col, const uint8_t* ref_depth, const int8_t* ref_qp0, const uint64_t* h_planes, int num_pics,
-                                          intptr_t stride, intptr_t cstride, x265amd_cu_stat* cu_stat, int ctu_addr, const uint8_t* ctx_in, uint64_t frac_in,
-                                          int16_t* coeff_out, x265amd_ctu_result* out)
-{
-    return compress_ctu_impl(me, stream, I, S, si, A, units, cur, col, ref_depth, ref_qp0, h_planes, num_pics, stride, cstride, cu_stat, ctu_addr, ctx_in, frac_in, coeff_out, out,
-                             (XaMapUnit*)xa_devmap_find(cur), (const XaMapUnit*)xa_devmap_find(col));
-}
 extern "C" int x265amd_compress_ctu_inter_ex(x265amd_me_ctx* me, void* stream, const x265amd_mvpred_info* I, const x265amd_inter_search_params* S,
                                              const x265amd_slice_info* si, const x265amd_analysis_params* A, x265amd_cu_unit* units, x265amd_mv_unit* cur,
                                              const x265amd_mv_unit* col, const uint8_t* ref_depth, const int8_t* ref_qp0, const uint64_t* h_planes, int num_pics,
                                              intptr_t stride, intptr_t cstride, x265amd_cu_stat* cu_stat, int ctu_addr, const uint8_t* ctx_in, uint64_t frac_in,
                                              int16_t* coeff_out, x265amd_ctu_result* out, const x265amd_rskip_edge* edge)
 {
-    return compress_ctu_impl(me, stream, I, S, si, A, units, cur, col, ref_depth, ref_qp0, h_planes, num_pics, stride, cstride, cu_stat, ctu_addr, ctx_in, frac_in, coeff_out, out,
-                             (XaMapUnit*)xa_devmap_find(cur), (const XaMapUnit*)xa_devmap_find(col), nullptr, nullptr, edge);
+    const XaAnalysisArgs pic = { me, I, S, si, A, units, cur, col, ref_depth, ref_qp0, h_planes, num_pics, stride, cstride, cu_stat, nullptr, nullptr, edge };
+    return xa_compress_ctu(pic, stream, ctu_addr, ctx_in, frac_in, coeff_out, out, (XaMapUnit*)xa_devmap_find(cur), (const XaMapUnit*)xa_devmap_find(col));
 }
-static int compress_ctu_impl(x265amd_me_ctx* me, void* stream, const x265amd_mvpred_info* I, const x265amd_inter_search_params* S,
-                             const x265amd_slice_info* si, const x265amd_analysis_params* A, x265amd_cu_unit* units, x265amd_mv_unit* cur,
-                             const x265amd_mv_unit* col, const uint8_t* ref_depth, const int8_t* ref_qp0, const uint64_t* h_planes, int num_pics,
-                             intptr_t stride, intptr_t cstride, x265amd_cu_stat* cu_stat, int ctu_addr, const uint8_t* ctx_in, uint64_t frac_in,
-                             int16_t* coeff_out, x265amd_ctu_result* out, XaMapUnit* dCur, const XaMapUnit* dCol, const int8_t* cu_qp, const XaTuRecs* tu_recs, const x265amd_rskip_edge* edge)
+extern "C" int x265amd_compress_ctu_inter(x265amd_me_ctx* me, void* stream, const x265amd_mvpred_info* I, const x265amd_inter_search_params* S,
+                                          const x265amd_slice_info* si, const x265amd_analysis_params* A, x265amd_cu_unit* units, x265amd_mv_unit* cur,
+                                          const x265amd_mv_unit* col, const uint8_t* ref_depth, const int8_t* ref_qp0, const uint64_t* h_planes, int num_pics,
+                                          intptr_t stride, intptr_t cstride, x265amd_cu_stat* cu_stat, int ctu_addr, const uint8_t* ctx_in, uint64_t frac_in,
+                                          int16_t* coeff_out, x265amd_ctu_result* out)
 {
+    return x265amd_compress_ctu_inter_ex(me, stream, I, S, si, A, units, cur, col, ref_depth, ref_qp0, h_planes, num_pics, stride, cstride, cu_stat, ctu_addr, ctx_in, frac_in,
+                                         coeff_out, out, nullptr);
+}
+int xa_compress_ctu(const XaAnalysisArgs& pic, void* stream, int ctu_addr, const uint8_t* ctx_in, uint64_t frac_in, int16_t* coeff_out, x265amd_ctu_result* out,
+                    XaMapUnit* dCur, const XaMapUnit* dCol)
+{
+    x265amd_me_ctx* const me = pic.me; const x265amd_mvpred_info* const I = pic.I; const x265amd_inter_search_params* const S = pic.S; const x265amd_slice_info* const si = pic.si;
+    const x265amd_analysis_params* const A = pic.A; x265amd_cu_unit* const units = pic.units; x265amd_mv_unit* const cur = pic.cur; const x265amd_mv_unit* const col = pic.col;
+    const uint8_t* const ref_depth = pic.ref_depth; const int8_t* const ref_qp0 = pic.ref_qp0; const uint64_t* const h_planes = pic.h_planes; const int num_pics = pic.num_pics;
+    const intptr_t stride = pic.stride, cstride = pic.cstride; x265amd_cu_stat* const cu_stat = pic.cu_stat; const int8_t* const cu_qp = pic.cu_qp; const XaTuRecs* const tu_recs = pic.tu_recs;
+    const x265amd_rskip_edge* const edge = pic.edge;
     if ((!me && si && si->slice_type != 2) || !I || !S || !si || !A || !units || !cur || !ref_depth || !ref_qp0 || !h_planes || !cu_stat || !ctx_in || !out || num_pics < 2)
         return xa_fail(X265AMD_EINVAL, "compress_ctu_inter: null argument");
     if (si->slice_type != 2 && (si->slice_type == 0) != (I->is_inter_b != 0)) return xa_fail(X265AMD_EINVAL, "compress_ctu_inter: slice type");
@@ -2445,351 +2294,5 @@ static int compress_ctu_impl(x265amd_me_ctx* me, void* stream, const x265amd_mvp
         fclose(dump);
     }
     { XA_HOSTPROF("ctu.delete Analyzer"); delete an; }
-    return rc;
-}
-
-/* The CTU loop of one frame: FrameEncoder::processRowEncoder (reference: source/encoder/frameencoder.cpp:1399-1700) without rate control,
- * VBV, slices or filters: every CTU in raster order (which respects the wavefront dependencies), its start state taken from the row coder
- * (one per row under WPP: row r > 0 starts from the state saved after the second CTU of row r - 1, frameencoder.cpp:1568-1573 / :1596-1598;
- * otherwise one coder runs through all rows), compressCTU, then the row coder codes the CTU in bit-counting mode to advance its state.
- * Without WPP the slice data can be written afterwards (FrameEncoder::encodeSlice, :1298-1370).
- * The reference's row coder only counts bits when SAO is on; without SAO it writes the final bitstream itself (frameencoder.cpp:683-699)
- * and its m_fracBits stays 0, so every CTU then starts from a zero bit fraction (ap->use_sao). */
-extern "C" int x265amd_analyse_frame(x265amd_me_ctx* me, void* stream, const x265amd_mvpred_info* I, const x265amd_inter_search_params* S,
-                                     const x265amd_slice_info* si, const x265amd_analysis_params* A, x265amd_cu_unit* units, x265amd_mv_unit* cur,
-                                     const x265amd_mv_unit* col, const uint8_t* ref_depth, const int8_t* ref_qp0, const uint64_t* h_planes, int num_pics,
-                                     intptr_t stride, intptr_t cstride, x265amd_cu_stat* cu_stat, int16_t* coeff_out, x265amd_ctu_result* results,
-                                     uint8_t* slice_data, size_t cap, uint32_t* substream_sizes, int* num_substreams)
-{
-    return xa_analyse_frame(me, stream, I, S, si, A, units, cur, col, ref_depth, ref_qp0, h_planes, num_pics, stride, cstride, cu_stat, coeff_out, results, slice_data, cap,
-                            substream_sizes, num_substreams, nullptr);
-}
-extern "C" int x265amd_analyse_frame_ex(x265amd_me_ctx* me, void* stream, const x265amd_mvpred_info* I, const x265amd_inter_search_params* S,
-                                        const x265amd_slice_info* si, const x265amd_analysis_params* A, x265amd_cu_unit* units, x265amd_mv_unit* cur,
-                                        const x265amd_mv_unit* col, const uint8_t* ref_depth, const int8_t* ref_qp0, const uint64_t* h_planes, int num_pics,
-                                        intptr_t stride, intptr_t cstride, x265amd_cu_stat* cu_stat, int16_t* coeff_out, x265amd_ctu_result* results,
-                                        uint8_t* slice_data, size_t cap, uint32_t* substream_sizes, int* num_substreams, const x265amd_rskip_edge* edge)
-{
-    return xa_analyse_frame(me, stream, I, S, si, A, units, cur, col, ref_depth, ref_qp0, h_planes, num_pics, stride, cstride, cu_stat, coeff_out, results, slice_data, cap,
-                            substream_sizes, num_substreams, nullptr, nullptr, nullptr, edge);
-}
-
-/* hooks (pictures coded in parallel, FrameEncoder::compressFrame's row loop, frameencoder.cpp:880-960): before_row blocks until the reference pictures have
- * finished the rows this CTU row may read; after_row hands the analysed row to the in-loop filters */
-int xa_analyse_frame(x265amd_me_ctx* me, void* stream, const x265amd_mvpred_info* I, const x265amd_inter_search_params* S,
-                     const x265amd_slice_info* si, const x265amd_analysis_params* A, x265amd_cu_unit* units, x265amd_mv_unit* cur,
-                     const x265amd_mv_unit* col, const uint8_t* ref_depth, const int8_t* ref_qp0, const uint64_t* h_planes, int num_pics,
-                     intptr_t stride, intptr_t cstride, x265amd_cu_stat* cu_stat, int16_t* coeff_out, x265amd_ctu_result* results,
-                     uint8_t* slice_data, size_t cap, uint32_t* substream_sizes, int* num_substreams, const XaRowHooks* hooks, const int8_t* cu_qp, const XaTuRecs* tu_recs, const x265amd_rskip_edge* edge)
-{
-    if (!I || !si || !units || !cur || !cu_stat || !coeff_out) return xa_fail(X265AMD_EINVAL, "analyse_frame: null argument");
-    const int ctuW = (si->pic_width + 63) >> 6, ctuH = (si->pic_height + 63) >> 6, numCtu = ctuW * ctuH, w4 = si->pic_width >> 2, h4 = si->pic_height >> 2;
-    for (int i = 0; i < w4 * h4; i++)
-    {
-        memset(&units[i], 0, sizeof(x265amd_cu_unit));
-        units[i].qp = (int8_t)si->slice_qp;
-        memset(&cur[i], 0, sizeof(x265amd_mv_unit));
-        cur[i].ref_idx[0] = cur[i].ref_idx[1] = -1;
-    }
-    memset(cu_stat, 0, sizeof(x265amd_cu_stat) * (numCtu + 1));          /* FrameData::reinit */
-    const bool wpp = si->wpp != 0;
-    /* the motion fields' mirrors in device memory (inter_chain_dev.h): the encoder object registers them with its pictures; other callers get them for the call */
-    struct TmpMap { const x265amd_mv_unit* h = nullptr; ~TmpMap() { if (h) xa_devmap_unregister(h); } } tmpCur, tmpCol;
-    XaMapUnit* frameDCur = (XaMapUnit*)xa_devmap_find(cur);
-    const XaMapUnit* frameDCol = (const XaMapUnit*)xa_devmap_find(col);
-    if (xa_queues_enabled() && !xa_env_present("X265AMD_DUMP_CTU"))
-    {
-        if (!frameDCur && (frameDCur = (XaMapUnit*)xa_devmap_register(cur, (size_t)w4 * h4)) != nullptr) tmpCur.h = cur;
-        if (col && !frameDCol && si->slice_type != 2 && (frameDCol = (const XaMapUnit*)xa_devmap_register(col, (size_t)w4 * h4)) != nullptr)
-        {
-            tmpCol.h = col;
-            for (int i = 0; i < w4 * h4; i++) devmap_store((XaMapUnit*)frameDCol + i, col[i], 0);
-        }
-    }
-    std::vector<x265amd_cabac*> rows(wpp ? ctuH : 1, nullptr);
-    for (size_t r = 0; r < rows.size(); r++)
-    {
-        rows[r] = x265amd_cabac_open(si, units, 1);
-        if (!rows[r]) { for (x265amd_cabac* c : rows) if (c) x265amd_cabac_close(c); return xa_fail(X265AMD_EINVAL, "analyse_frame: slice description"); }
-    }
-    std::vector<uint8_t> buffered((size_t)ctuH * X265AMD_CTX_STRIDE, 0);
-    int rc = X265AMD_OK;
-    /* one CTU: analysis with the row coder's state, then the row coder codes it (bits only) to carry the contexts on */
-    auto doCtu = [&](int addr, void* st) -> int {
-        const int row = addr / ctuW, colIdx = addr % ctuW;
-        x265amd_cabac* rowCoder = rows[wpp ? row : 0];
-        if (wpp && !colIdx && row)
-        {
-            /* copyState(m_initSliceContext) + loadContexts(bufferedEntropy of the row above) */
-            memcpy(rowCoder->ctx, &buffered[(size_t)(row - 1) * X265AMD_CTX_STRIDE], X265AMD_CTX_STRIDE);
-            rowCoder->fracBits = 0;
-        }
-        x265amd_ctu_result res;
-        int16_t* coeff = coeff_out + (size_t)addr * kTileElems;
-        int r = compress_ctu_impl(me, st, I, S, si, A, units, cur, col, ref_depth, ref_qp0, h_planes, num_pics, stride, cstride, cu_stat, addr,
-                                  rowCoder->ctx, A->use_sao ? rowCoder->fracBits : 0, coeff, &res, frameDCur, frameDCol, cu_qp, tu_recs, edge);
-        if (r != X265AMD_OK) return r;
-        if (results) results[addr] = res;
-        xa_phase(XA_PH_ANALYZER);
-        { XA_HOSTPROF("row.cabac_encode_ctu"); r = x265amd_cabac_encode_ctu(rowCoder, addr, coeff, coeff + 4096, coeff + 5120); }
-        xa_phase(XA_PH_CABAC_CTU);
-        if (wpp && colIdx == 1) memcpy(&buffered[(size_t)row * X265AMD_CTX_STRIDE], rowCoder->ctx, X265AMD_CTX_STRIDE);
-        return r;
-    };
-    int rowThreads = 1;
-    if (wpp && ctuH > 1 && ctuW > 1)
-    {
-        const char* e = xa_env_str("X265AMD_ROW_THREADS");
-        rowThreads = e ? atoi(e) : 64;        /* the wavefront never holds more than min(rows, columns / 2) CTUs at once */
-        if (rowThreads > ctuH) rowThreads = ctuH;
-        if (rowThreads > (ctuW + 1) / 2) rowThreads = (ctuW + 1) / 2;
-    }
-    const bool dumping = xa_env_present("X265AMD_DUMP_CTU");        /* the dump synchronises the device: not behind a resident kernel */
-    if (rowThreads <= 1)
-    {
-        if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) rc = xa_fail(X265AMD_EHIP, "analyse_frame: synchronize");
-        void* q = dumping ? nullptr : xa_queue_acquire();
-        for (int addr = 0; addr < numCtu && rc == X265AMD_OK; addr++)
-        {
-            if (hooks && addr % ctuW == 0)
-            {
-                struct W { const XaRowHooks* h; int row; } w{ hooks, addr / ctuW };
-                xa_wait_until([](void* c) -> int { W* x = (W*)c; return x->h->row_ready(x->h->ctx, x->row) != 0; }, &w);
-                if (hooks->row_ready(hooks->ctx, addr / ctuW) < 0) { rc = xa_fail(X265AMD_EHIP, "analyse_frame: a reference picture failed"); break; }
-                hooks->before_row(hooks->ctx, addr / ctuW);
-            }
-            if (hooks && hooks->ctu_wait && hooks->ctu_wait(hooks->ctx, addr / ctuW, addr % ctuW)) { rc = xa_fail(X265AMD_EHIP, "analyse_frame: a reference picture failed"); break; }
-            if (hooks && hooks->before_ctu) hooks->before_ctu(hooks->ctx, addr / ctuW, addr % ctuW);
-            rc = doCtu(addr, q ? q : stream);
-            if (rc == X265AMD_OK && xa_stream_sync(q ? q : stream) != hipSuccess) rc = xa_fail(X265AMD_EHIP, "analyse_frame: synchronize");
-            if (hooks && rc == X265AMD_OK && hooks->after_ctu) hooks->after_ctu(hooks->ctx, addr / ctuW, addr % ctuW);
-            if (hooks && rc == X265AMD_OK && addr % ctuW == ctuW - 1) hooks->after_row(hooks->ctx, addr / ctuW);
-        }
-        if (q) xa_queue_release(q);
-    }
-    else
-    {
-        /* Wavefront parallel processing as the reference's row jobs run it (frameencoder.cpp:1399-1968): CTU (r, c) starts when (r - 1, c + 1)
-         * is finished -- its neighbours' decisions, reconstruction, cost statistics and the contexts saved after (r - 1, 1) are then final, so
-         * every CTU sees exactly what the serial order shows it.  Every CTU row is a task on the worker threads (xa_fiber.h) with a device job queue
-         * while it runs; the block operations of different rows overlap on the device, and a row that waits (for the device, for the row above, for
-         * a reference picture) leaves its worker thread to the rows that can go on.  A row takes its queue only when the reference pictures let it
-         * start and after the row above has taken one, and gives it back at the end of the row: every held queue belongs to a row that can run,
-         * whatever the number of pictures in flight, so waiting for a queue always ends. */
-        if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) rc = xa_fail(X265AMD_EHIP, "analyse_frame: synchronize");
-        struct Frame
-        {
-            std::vector<volatile uint64_t*> done;   /* CTUs finished per row: counters the parked rows below wait on (xa_fiber.h) */
-            volatile uint64_t* queuedRows;          /* rows that hold (or have held) a queue */
-            std::atomic<int> firstErr{ X265AMD_OK };
-            const XaRowHooks* hooks; int ctuW, ctuH; bool dumping; int poc; bool intraOnly, intraTry, pSlice;
-            std::function<int(int, void*)> doCtu;
-            explicit Frame(int rowsN) : done(rowsN) { for (auto& d : done) d = xa_counter_alloc(); queuedRows = xa_counter_alloc(); }
-            ~Frame() { for (auto& d : done) xa_counter_free(d); xa_counter_free(queuedRows); }
-        } F(ctuH);
-        F.hooks = hooks; F.ctuW = ctuW; F.ctuH = ctuH; F.dumping = dumping; F.poc = I->poc; F.doCtu = doCtu; F.intraOnly = si->slice_type == 2; F.pSlice = si->slice_type == 1;
-        F.intraTry = si->slice_type == 1 || (si->slice_type == 0 && A->b_intra);       /* pictures whose CUs try intra beside their inter modes */
-        struct Row { Frame* f; int row; };
-        std::vector<Row> rowsArg((size_t)ctuH);
-        std::vector<XaTask> tasks((size_t)ctuH);
-        static std::atomic<uint64_t> frameSeq{ 0 };
-        const uint64_t seqCall = frameSeq.fetch_add(1);     /* analyses start in coding order: older pictures' rows go first */
-        const uint64_t seq = hooks && hooks->order ? hooks->order : seqCall;
-        auto rowReady = [](void* c) -> int {
-            Row* r = (Row*)c; Frame& f = *r->f;
-            if (f.firstErr.load() != X265AMD_OK) return 1;
-            return f.hooks ? f.hooks->row_ready(f.hooks->ctx, r->row) != 0 : 1;
-        };
-        auto rowMain = [](void* c) {
-            Row* r = (Row*)c; Frame& f = *r->f;
-            const int row = r->row, ctuW = f.ctuW;
-            const auto tStart = std::chrono::steady_clock::now();
-            if (void** slot = xa_task_slot()) *slot = (void*)f.hooks;          /* the guards of this row's reference reads (xa_ref_guard_*) */
-            if (f.hooks && f.firstErr.load() == X265AMD_OK)
-            {
-                if (f.hooks->row_ready(f.hooks->ctx, row) < 0) { int ok = X265AMD_OK; f.firstErr.compare_exchange_strong(ok, xa_fail(X265AMD_EHIP, "analyse_frame: a reference picture failed")); }
-                else f.hooks->before_row(f.hooks->ctx, row);
-            }
-            void* st = f.dumping ? nullptr : xa_queue_acquire();
-            hipStream_t own = nullptr;
-            if (!st)
-            {
-                if (hipStreamCreateWithFlags(&own, hipStreamNonBlocking) != hipSuccess) { int ok = X265AMD_OK; f.firstErr.compare_exchange_strong(ok, xa_fail(X265AMD_EHIP, "analyse_frame: stream")); }
-                st = own;
-            }
-            {
-                static const char* const lg = xa_env_str("X265AMD_QUEUE_LOG");
-                int lp = -1, lr = -1;
-                if (lg && sscanf(lg, "%d,%d", &lp, &lr) == 2 && lp == f.poc && lr == row && st && !own) xa_queue_log(st, lp, lr);
-            }
-            /* I pictures: a second queue for the row when one is to spare -- the two partitionings of an 8x8 CU are evaluated side by side (intra_rd.hip) */
-            void* helper = (f.intraOnly && st && !own) ? xa_queue_try_acquire() : nullptr;
-            void* helper2 = helper ? xa_queue_try_acquire() : nullptr;         /* and a third and a fourth: the 16x16 / 32x32 CUs' 2Nx2N evaluations beside their sub-CUs */
-            void* helper3 = helper2 ? xa_queue_try_acquire() : nullptr;
-            /* P pictures: a second queue for the searches that start ahead of their CU's merge check (Analyzer::searchAhead) */
-            const int auxSpare = 112;       /* (an I picture started meanwhile needs four queues per row) */
-            void* aux = (f.pSlice && st && !own) ? xa_queue_try_acquire_spare(auxSpare) : nullptr;
-            void* aux2 = aux ? xa_queue_try_acquire_spare(auxSpare) : nullptr;                /* and a third for the searches of CUs whose sub-CUs come first */
-            if (aux) xa_queue_set_aux(st, aux);
-            if (aux2) xa_queue_set_aux(aux, aux2);
-            if (helper) xa_queue_set_helper(st, helper);
-            if (helper2) xa_queue_set_helper(helper, helper2);
-            if (helper3) xa_queue_set_helper(helper2, helper3);
-            std::atomic_thread_fence(std::memory_order_release);
-            *f.queuedRows = (uint64_t)(row + 1);
-            const auto tQueue = std::chrono::steady_clock::now();
-            for (int c2 = 0; c2 < ctuW; c2++)
-            {
-                /* a row of an I picture that started while every queue was taken (the picture behind a scene cut starts beside the pictures in front of it) asks again:
-                 * without its second to fourth queue its CTUs take twice as long */
-                /* a row of a P picture likewise: the rows that started while an I picture held the queues (in lockstep behind it) are the ones still running when it has
-                 * ended -- the tail of the clip, where every link is a last-column CTU searched CU by CU -- and the searches ahead of the merge checks need the second and third queue */
-                if (f.pSlice && st && !own && !aux2)
-                {
-                    if (!aux) { aux = xa_queue_try_acquire_spare(auxSpare); if (aux) xa_queue_set_aux(st, aux); }
-                    if (aux && !aux2) { aux2 = xa_queue_try_acquire_spare(auxSpare); if (aux2) xa_queue_set_aux(aux, aux2); }
-                }
-                if (f.intraOnly && st && !own && !helper3)
-                {
-                    if (!helper) { helper = xa_queue_try_acquire(); if (helper) xa_queue_set_helper(st, helper); }
-                    if (helper && !helper2) { helper2 = xa_queue_try_acquire(); if (helper2) xa_queue_set_helper(helper, helper2); }
-                    if (helper2 && !helper3) { helper3 = xa_queue_try_acquire(); if (helper3) xa_queue_set_helper(helper2, helper3); }
-                }
-                if (row)
-                {
-                    const int need = c2 + 2 < ctuW ? c2 + 2 : ctuW;
-                    const auto w0 = std::chrono::steady_clock::now();
-                    const int wc = xa_task_wait_class(1);
-                    xa_wait_counter(f.done[row - 1], (uint64_t)need);          /* a failing row sets its counter to the end, so this always ends */
-                    xa_task_wait_class(wc);
-                    std::atomic_thread_fence(std::memory_order_acquire);
-                    xa_prof_dependency_wait((uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - w0).count());
-                }
-                int r2 = f.firstErr.load();
-                if (r2 == X265AMD_OK && !st) r2 = X265AMD_EHIP;
-                /* the reference pictures are published column by column: this CTU follows them (parked on their counters meanwhile) */
-                static const bool ctuLog = xa_env_present("X265AMD_CTU_LOG");
-                static const int ctuLogPoc = ctuLog && xa_env_str("X265AMD_CTU_LOG")[0] == 'p' ? atoi(xa_env_str("X265AMD_CTU_LOG") + 1) : -1;       /* "p9": every row of picture 9; anything else: the last three rows of every picture */
-                static const auto tLog0 = std::chrono::steady_clock::time_point() + std::chrono::duration_cast<std::chrono::steady_clock::duration>(std::chrono::duration<double, std::milli>(
-                    floor(std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count() / 1e6) * 1e6));       /* milliseconds modulo 10^6 of the steady clock: X265AMD_PUB_LOG's clock */
-                const double tA = ctuLog ? std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tLog0).count() : 0;
-                const int wc2 = xa_task_wait_class(2);
-                if (r2 == X265AMD_OK && f.hooks && f.hooks->ctu_wait && f.hooks->ctu_wait(f.hooks->ctx, row, c2)) r2 = xa_fail(X265AMD_EHIP, "analyse_frame: a reference picture failed");
-                xa_task_wait_class(wc2);
-                const double tB = ctuLog ? std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tLog0).count() : 0;
-                struct CtuLog { bool on; int poc, row, col; double a, b; uint64_t p0[4], run0;
-                                ~CtuLog() { if (!on) return; uint64_t p1[4]; xa_task_parked_ns(p1);
-                                            fprintf(stderr, "x265amd ctu: poc %d row %d col %d: row-above wait from %.2f, gate passed %.2f, done %.2f; in the CTU: running %.2f, waiting for the device %.2f, for reference samples %.2f\n", poc, row, col, a, b,
-                                                    std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tLog0).count(), (xa_task_run_ns_always() - run0) / 1e6, (p1[0] - p0[0]) / 1e6, (p1[3] - p0[3]) / 1e6); } }
-                    ctuLogger{ ctuLog && (ctuLogPoc >= 0 ? f.poc == ctuLogPoc : row >= f.ctuH - 3), f.poc, row, c2, tA, tB, { 0, 0, 0, 0 }, 0 };
-                if (ctuLogger.on) { xa_task_parked_ns(ctuLogger.p0); ctuLogger.run0 = xa_task_run_ns_always(); }
-                if (r2 == X265AMD_OK && f.hooks && f.hooks->before_ctu) f.hooks->before_ctu(f.hooks->ctx, row, c2);
-                if (r2 == X265AMD_OK) r2 = f.doCtu(row * ctuW + c2, st);
-                if (r2 == X265AMD_OK && xa_stream_sync(st) != hipSuccess) r2 = xa_fail(X265AMD_EHIP, "analyse_frame: row stream");
-                if (r2 != X265AMD_OK) { int ok = X265AMD_OK; f.firstErr.compare_exchange_strong(ok, r2); }
-                std::atomic_thread_fence(std::memory_order_release);
-                *f.done[row] = (uint64_t)(c2 + 1);
-                if (r2 != X265AMD_OK) break;
-                if (f.hooks && f.hooks->after_ctu) f.hooks->after_ctu(f.hooks->ctx, row, c2);
-                if (f.hooks && c2 == ctuW - 1) f.hooks->after_row(f.hooks->ctx, row);
-            }
-            if (f.firstErr.load() != X265AMD_OK) *f.done[row] = (uint64_t)ctuW;
-            if (aux2) { xa_queue_set_aux(aux, nullptr); xa_queue_release_helper(aux2); }
-            if (aux) { xa_queue_set_aux(st, nullptr); xa_queue_release_helper(aux); }
-            if (helper3) { xa_queue_set_helper(helper2, nullptr); xa_queue_release_helper(helper3); }
-            if (helper2) { xa_queue_set_helper(helper, nullptr); xa_queue_release_helper(helper2); }
-            if (helper) { xa_queue_set_helper(st, nullptr); xa_queue_release_helper(helper); }
-            if (own) (void)hipStreamDestroy(own);
-            else if (st) xa_queue_release(st);
-            if (g_timing && f.hooks)
-            {
-                static const auto t00 = std::chrono::steady_clock::now();
-                auto ms = [&](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(t - t00).count(); };
-                fprintf(stderr, "x265amd: row: poc %d row %d start %.1f queue %.1f end %.1f ran %.1f\n", f.poc, row, ms(tStart), ms(tQueue), ms(std::chrono::steady_clock::now()), xa_task_run_ns() / 1e6);
-            }
-        };
-        for (int r = 0; r < ctuH; r++)
-        {
-            rowsArg[r] = Row{ &F, r };
-            tasks[r].fn = rowMain; tasks[r].arg = &rowsArg[r]; tasks[r].ready = rowReady; tasks[r].readyCtx = &rowsArg[r];
-            tasks[r].startCounter = F.queuedRows; tasks[r].startValue = (uint64_t)r;          /* after the row above has taken its queue */
-            tasks[r].priority = (seq << 12) | (uint64_t)r;
-        }
-        if (rc == X265AMD_OK)
-        {
-            xa_tasks_run(tasks.data(), ctuH);
-            rc = F.firstErr.load();
-            if (rc != X265AMD_OK) xa_fail(rc, "analyse_frame: a CTU row failed");
-        }
-    }
-    for (x265amd_cabac* c : rows) x265amd_cabac_close(c);
-    if (g_timing)
-    {
-        uint64_t ss[3];
-        xa_sched_stats(ss);
-        xa_phase_report();
-        fprintf(stderr, "x265amd: workers so far: %.1f ms running tasks, %.1f ms looking for one, %llu switches\n", ss[0] / 1e6, ss[1] / 1e6, (unsigned long long)ss[2]);
-        fprintf(stderr, "x265amd: skip chains so far: %llu commands, %llu CUs skipped on the device, stopped %llu times at a CU that is not skipped and %llu times at a vector beyond what is published; "
-                "device ms: candidates %.1f, predictions + SA8D %.1f, choice %.1f, transform units %.1f, rate-distortion %.1f, placing %.1f, coder state %.1f (%llu CUs)\n", (unsigned long long)g_chainStat[0].load(),
-                (unsigned long long)g_chainStat[1].load(), (unsigned long long)g_chainStat[2].load(), (unsigned long long)g_chainStat[3].load(), g_chainTicks[0].load() / 1e5, g_chainTicks[1].load() / 1e5,
-                g_chainTicks[2].load() / 1e5, g_chainTicks[3].load() / 1e5, g_chainTicks[4].load() / 1e5, g_chainTicks[5].load() / 1e5, g_chainTicks[7].load() / 1e5, (unsigned long long)g_chainTicks[6].load());
-        fprintf(stderr, "x265amd: searches started ahead so far: %llu beside a leaf's merge check, %llu behind the merge check of a CU with sub-CUs; collected %llu, ruled out by the sub-CUs' reference pictures %llu\n",
-                (unsigned long long)g_aheadStat[0].load(), (unsigned long long)g_aheadStat[2].load(), (unsigned long long)g_aheadStat[1].load(), (unsigned long long)g_aheadStat[3].load());
-        for (int t = 0; t < 2; t++)
-            fprintf(stderr, "x265amd: CUs of %s pictures so far by depth 0..3 (skipped on the device / merge check on the host / searched / intra try): %llu/%llu/%llu/%llu %llu/%llu/%llu/%llu %llu/%llu/%llu/%llu %llu/%llu/%llu/%llu\n",
-                    t ? "P" : "B", (unsigned long long)g_cuStat[t][0][0].load(), (unsigned long long)g_cuStat[t][0][1].load(), (unsigned long long)g_cuStat[t][0][2].load(), (unsigned long long)g_cuStat[t][0][3].load(),
-                    (unsigned long long)g_cuStat[t][1][0].load(), (unsigned long long)g_cuStat[t][1][1].load(), (unsigned long long)g_cuStat[t][1][2].load(), (unsigned long long)g_cuStat[t][1][3].load(),
-                    (unsigned long long)g_cuStat[t][2][0].load(), (unsigned long long)g_cuStat[t][2][1].load(), (unsigned long long)g_cuStat[t][2][2].load(), (unsigned long long)g_cuStat[t][2][3].load(),
-                    (unsigned long long)g_cuStat[t][3][0].load(), (unsigned long long)g_cuStat[t][3][1].load(), (unsigned long long)g_cuStat[t][3][2].load(), (unsigned long long)g_cuStat[t][3][3].load());
-        fprintf(stderr, "x265amd: analysis stages (ms):");
-        for (int k = 0; k < 5; k++) { fprintf(stderr, " %s %.1f", g_stageName[k], g_stageMs[k]); g_stageMs[k] = 0; }
-        fprintf(stderr, "\n");
-    }
-    if (rc == X265AMD_OK && slice_data && substream_sizes && num_substreams)
-    {
-        if (A->use_sao) return xa_fail(X265AMD_EINVAL, "analyse_frame: with SAO the slice data follows the SAO decision: call x265amd_encode_slice_data afterwards");
-        rc = x265amd_encode_slice_data(si, units, coeff_out, nullptr, nullptr, slice_data, cap, substream_sizes, num_substreams);
-    }
-    return rc;
-}
-
-/* FrameEncoder::encodeSlice (frameencoder.cpp:1298-1370): the final CABAC pass over the decided picture.  One sub-stream per CTU row under WPP
- * (each row starts from the state saved after the second CTU of the row above and ends with finishSlice), otherwise one for the picture; the
- * SAO syntax of a CTU precedes its coding tree when the slice uses SAO. */
-extern "C" int x265amd_encode_slice_data(const x265amd_slice_info* si, x265amd_cu_unit* units, const int16_t* coeffs, const x265amd_sao_ctu* sao,
-                                         const int32_t* sao_flags, uint8_t* slice_data, size_t cap, uint32_t* substream_sizes, int* num_substreams)
-{
-    if (!si || !units || !coeffs || !slice_data || !substream_sizes || !num_substreams) return xa_fail(X265AMD_EINVAL, "encode_slice_data: null argument");
-    const int ctuW = (si->pic_width + 63) >> 6, ctuH = (si->pic_height + 63) >> 6, numCtu = ctuW * ctuH;
-    const bool wpp = si->wpp != 0;
-    std::vector<uint8_t> buffered((size_t)ctuH * X265AMD_CTX_STRIDE, 0);
-    size_t total = 0;
-    int count = 0, rc = X265AMD_OK;
-    x265amd_cabac* w = nullptr;
-    for (int addr = 0; addr < numCtu && rc == X265AMD_OK; addr++)
-    {
-        const int row = addr / ctuW, colIdx = addr % ctuW;
-        if (!w)
-        {
-            w = x265amd_cabac_open(si, units, 0);
-            if (!w) return xa_fail(X265AMD_EINVAL, "encode_slice_data: slice description");
-            if (wpp && row) memcpy(w->ctx, &buffered[(size_t)(row - 1) * X265AMD_CTX_STRIDE], X265AMD_CTX_STRIDE);
-        }
-        if (sao && sao_flags) w->saoCtu(colIdx, row == 0, sao[addr], sao_flags[0] != 0, sao_flags[1] != 0);
-        const int16_t* coeff = coeffs + (size_t)addr * kTileElems;
-        rc = x265amd_cabac_encode_ctu(w, addr, coeff, coeff + 4096, coeff + 5120);
-        if (wpp && colIdx == 1) memcpy(&buffered[(size_t)row * X265AMD_CTX_STRIDE], w->ctx, X265AMD_CTX_STRIDE);
-        if ((wpp && colIdx == ctuW - 1) || addr == numCtu - 1)
-        {
-            const size_t n = x265amd_cabac_finish_slice(w, slice_data + total, cap > total ? cap - total : 0);
-            if (total + n > cap) rc = xa_fail(X265AMD_EINVAL, "encode_slice_data: buffer too small");
-            substream_sizes[count++] = (uint32_t)n;
-            total += n;
-            x265amd_cabac_close(w);
-            w = nullptr;
-        }
-    }
-    if (w) x265amd_cabac_close(w);
-    *num_substreams = count;
     return rc;
 }

@@ -203,6 +203,32 @@ int x265amd_encoder::measureQuality(Pic& pic, hipStream_t st)
     return X265AMD_OK;
 }
 
+/* the buffers one picture's analysis reads and fills, and the slice data behind it (runFrame, runFrameParallel) */
+struct FrameBufs
+{
+    std::vector<x265amd_mv_unit> noCol;                 /* all zero: the collocated field of a picture that has none */
+    std::vector<uint8_t> refDepth; std::vector<int8_t> refQp0;         /* per list, of its first picture: the units' depths, CUData::m_qp[0] of the CTUs */
+    std::vector<x265amd_cu_stat> stat; std::vector<int16_t> coeff; std::vector<uint8_t> data; std::vector<uint32_t> sizes; int nsub = 0;
+    XaTuRecs tuRecs = { nullptr, { nullptr, nullptr } };
+    x265amd_rskip_edge edge = { nullptr, 0, 0.0f };     /* (an I picture never asks: its record goes in without counts) */
+    FrameBufs(const x265amd_encoder& e, const FrameCtx& fc)
+        : noCol(fc.colPic ? 0 : (size_t)e.w4 * e.h4), refDepth(2 * (size_t)e.w4 * e.h4, 0), refQp0(2 * (size_t)e.nctu, 0), stat((size_t)e.nctu + 1),
+          coeff((size_t)e.nctu * RD_TILE_ELEMS, 0), data((size_t)e.W * e.H * 3 + (1u << 16)), sizes((size_t)e.ctuH + 1, 0) {}
+};
+/* the picture as the analysis takes it (x265amd_host.h); pic.units, pic.motion and pic.tuRecs have their sizes by now */
+static XaAnalysisArgs analysisArgs(const x265amd_encoder& e, Pic& pic, FrameCtx& fc, FrameBufs& b)
+{
+    const bool limitTU = e.p.limitTU >= 3;
+    if (limitTU)
+    {
+        b.tuRecs.cur = pic.tuRecs.data();
+        for (int l = 0; l < 2; l++) if (!pic.lists[l].empty() && pic.lists[l][0]->tuRecs.size() == pic.tuRecs.size()) b.tuRecs.ref[l] = pic.lists[l][0]->tuRecs.data();
+    }
+    return { e.me, &fc.info, &fc.sp, &fc.si, &fc.ap, pic.units.data(), pic.motion.data(), fc.colPic ? fc.colPic->motion.data() : b.noCol.data(), b.refDepth.data(), b.refQp0.data(),
+             fc.planes.data(), (int)(fc.planes.size() / 3), e.stride, e.cstride, b.stat.data(), e.useDqp ? pic.cuQp.data() : nullptr, limitTU ? &b.tuRecs : nullptr,
+             e.p.recursionSkipMode == 2 ? &b.edge : nullptr };
+}
+
 /* FrameEncoder::compressFrame for one picture (its own thread and HIP stream).  The analysis starts when every reference picture is final; the
  * in-loop filters, SAO (its decision carries state from picture to picture, SAO::m_depthSaoRate) and the shared filter scratch run in coding
  * order, i.e. after the previous picture's task. */
@@ -220,50 +246,25 @@ int x265amd_encoder::runFrame(const PicP& picp, std::shared_future<int> prev)
     if (fc.failed) return xa_fail(X265AMD_EHIP, "encoder: weighted reference planes");
     for (auto& wpl : fc.wplanes)            /* one picture at a time: the reference pictures are complete, so are their weighted copies */
         if (weightRows(*wpl, 0, ctuH - 1) != X265AMD_OK) return X265AMD_EHIP;
-    const int stype = fc.stype;
-    std::vector<uint64_t>& planes = fc.planes;
     x265amd_mvpred_info& info = fc.info;
-    x265amd_inter_search_params& sp = fc.sp;
     x265amd_slice_info& si = fc.si;
-    x265amd_analysis_params& ap = fc.ap;
-    const Pic* colPic = fc.colPic;
-    (void)stype;
 
     const size_t nUnits = (size_t)w4 * h4;
     pic.units.assign(nUnits, x265amd_cu_unit()); pic.motion.assign(nUnits, x265amd_mv_unit());
     memset(pic.units.data(), 0, sizeof(x265amd_cu_unit) * nUnits); memset(pic.motion.data(), 0, sizeof(x265amd_mv_unit) * nUnits);
-    std::vector<x265amd_mv_unit> noCol;
-    if (!colPic) { noCol.resize(nUnits); memset(noCol.data(), 0, sizeof(x265amd_mv_unit) * nUnits); }
-    std::vector<uint8_t> refDepth(2 * nUnits, 0);
-    std::vector<int8_t> refQp0(2 * (size_t)nctu, 0);
+    FrameBufs bufs(*this, fc);
     for (int l = 0; l < 2; l++)
         if (!lists[l].empty())
         {
             const Pic* q = lists[l][0].get();
-            for (size_t i = 0; i < nUnits; i++) refDepth[l * nUnits + i] = q->units[i].depth;
-            for (int i = 0; i < nctu; i++) refQp0[(size_t)l * nctu + i] = useDqp ? q->units[(size_t)(i / ctuW) * 16 * w4 + (size_t)(i % ctuW) * 16].qp : (int8_t)q->sliceQp;      /* CUData::m_qp[0] of the co-located CTU */
+            for (size_t i = 0; i < nUnits; i++) bufs.refDepth[l * nUnits + i] = q->units[i].depth;
+            for (int i = 0; i < nctu; i++) bufs.refQp0[(size_t)l * nctu + i] = useDqp ? q->units[(size_t)(i / ctuW) * 16 * w4 + (size_t)(i % ctuW) * 16].qp : (int8_t)q->sliceQp;      /* CUData::m_qp[0] of the co-located CTU */
         }
-    std::vector<x265amd_cu_stat> stat((size_t)nctu + 1);
-    memset(stat.data(), 0, sizeof(x265amd_cu_stat) * stat.size());
-    std::vector<int16_t> coeff((size_t)nctu * RD_TILE_ELEMS, 0);
-    std::vector<uint8_t> data((size_t)W * H * 3 + (1u << 16));
-    std::vector<uint32_t> sizes((size_t)ctuH + 1, 0);
-    int nsub = 0;
     const bool sao = p.bEnableSAO != 0;
     if (useDqp && pic.cuQp.empty()) return xa_fail(X265AMD_EINVAL, "encoder: the picture has no CU QPs");
-    XaTuRecs tuRecs = { nullptr, { nullptr, nullptr } };
-    if (p.limitTU >= 3)
-    {
-        pic.tuRecs.assign((size_t)nctu * 21, -1);
-        tuRecs.cur = pic.tuRecs.data();
-        for (int l = 0; l < 2; l++) if (!pic.lists[l].empty() && pic.lists[l][0]->tuRecs.size() == pic.tuRecs.size()) tuRecs.ref[l] = pic.lists[l][0]->tuRecs.data();
-    }
-    x265amd_rskip_edge edge = { nullptr, 0, 0.0f };
-    const bool useEdge = p.recursionSkipMode == 2;          /* (an I picture never asks: its record goes in without counts) */
-    if (useEdge && si.slice_type != 2) { const int erc = edgeCounts(pic, st, edge); if (erc != X265AMD_OK) return erc; }
-    int rc = xa_analyse_frame(me, st, &info, &sp, &si, &ap, pic.units.data(), pic.motion.data(), colPic ? colPic->motion.data() : noCol.data(),
-                              refDepth.data(), refQp0.data(), planes.data(), (int)(planes.size() / 3), stride, cstride, stat.data(), coeff.data(), nullptr,
-                              sao ? nullptr : data.data(), data.size(), sizes.data(), &nsub, nullptr, useDqp ? pic.cuQp.data() : nullptr, p.limitTU >= 3 ? &tuRecs : nullptr, useEdge ? &edge : nullptr);
+    if (p.limitTU >= 3) pic.tuRecs.assign((size_t)nctu * 21, -1);
+    if (p.recursionSkipMode == 2 && si.slice_type != 2) { const int erc = edgeCounts(pic, st, bufs.edge); if (erc != X265AMD_OK) return erc; }
+    int rc = xa_analyse_frame(analysisArgs(*this, pic, fc, bufs), st, bufs.coeff.data(), nullptr, sao ? nullptr : bufs.data.data(), bufs.data.size(), bufs.sizes.data(), &bufs.nsub, nullptr);
     if (rc != X265AMD_OK) return rc;
     if (hipStreamSynchronize(st) != hipSuccess) return xa_fail(X265AMD_EHIP, "encoder: analysis");
 
@@ -308,7 +309,7 @@ int x265amd_encoder::runFrame(const PicP& picp, std::shared_future<int> prev)
         if (hipStreamSynchronize(st) != hipSuccess) return xa_fail(X265AMD_EHIP, "encoder: sao");
         std::swap(pic.dRec, dSaoTmp);
         recY = pic.dRec + org[0]; recU = pic.dRec + org[1]; recV = pic.dRec + org[2];
-        rc = x265amd_encode_slice_data(&si, pic.units.data(), coeff.data(), sparams.data(), saoFlags, data.data(), data.size(), sizes.data(), &nsub);
+        rc = x265amd_encode_slice_data(&si, pic.units.data(), bufs.coeff.data(), sparams.data(), saoFlags, bufs.data.data(), bufs.data.size(), bufs.sizes.data(), &bufs.nsub);
         if (rc != X265AMD_OK) return rc;
     }
     /* the reconstruction becomes a reference: extend its borders */
@@ -319,7 +320,7 @@ int x265amd_encoder::runFrame(const PicP& picp, std::shared_future<int> prev)
     if (hipStreamSynchronize(st) != hipSuccess) return xa_fail(X265AMD_EHIP, "encoder: border extension");
     if (p.bEnablePsnr || p.bEnableSsim) { rc = measureQuality(pic, st); if (rc != X265AMD_OK) return rc; }
 
-    rc = sliceNal(*this, pic, fc, saoFlags, data, sizes, nsub);
+    rc = sliceNal(*this, pic, fc, saoFlags, bufs.data, bufs.sizes, bufs.nsub);
     if (rc) return rc;
     /* the source is no longer needed (unless the weight analysis of later pictures reads its chroma planes: weightAnalyse works on source pictures); the reconstruction
      * stays while the picture is referenced.  The reference lists are only needed by pictures that are still to come through their own lists */
@@ -769,26 +770,15 @@ int x265amd_encoder::runFrameParallel(const PicP& picp)
     const std::vector<PicP>* lists = pic.lists;
     FrameCtx fc;
     frameContext(*this, pic, fc);
-    const Pic* colPic = fc.colPic;
-    const size_t nUnits = (size_t)w4 * h4;
-    std::vector<x265amd_mv_unit> noCol;
-    if (!colPic) { noCol.resize(nUnits); memset(noCol.data(), 0, sizeof(x265amd_mv_unit) * nUnits); }
-    std::vector<uint8_t> refDepth(2 * nUnits, 0);
-    std::vector<int8_t> refQp0(2 * (size_t)nctu, 0);
     if (fc.failed) return xa_fail(X265AMD_EHIP, "encoder: weighted reference planes");
-    RowGate gate{ this, &pic, {}, &refDepth, nUnits, &fc, &refQp0 };
+    FrameBufs bufs(*this, fc);
+    RowGate gate{ this, &pic, {}, &bufs.refDepth, (size_t)w4 * h4, &fc, &bufs.refQp0 };
     if (useDqp && pic.cuQp.empty()) return xa_fail(X265AMD_EINVAL, "encoder: the picture has no CU QPs");
     for (int l = 0; l < 2; l++)
     {
         for (const PicP& q : lists[l]) if (std::find(gate.refs.begin(), gate.refs.end(), q.get()) == gate.refs.end()) gate.refs.push_back(q.get());
-        if (!lists[l].empty()) for (int i = 0; i < nctu; i++) refQp0[(size_t)l * nctu + i] = (int8_t)lists[l][0]->sliceQp;
+        if (!lists[l].empty()) for (int i = 0; i < nctu; i++) bufs.refQp0[(size_t)l * nctu + i] = (int8_t)lists[l][0]->sliceQp;
     }
-    std::vector<x265amd_cu_stat> stat((size_t)nctu + 1);
-    memset(stat.data(), 0, sizeof(x265amd_cu_stat) * stat.size());
-    std::vector<int16_t> coeff((size_t)nctu * RD_TILE_ELEMS, 0);
-    std::vector<uint8_t> data((size_t)W * H * 3 + (1u << 16));
-    std::vector<uint32_t> sizes((size_t)ctuH + 1, 0);
-    int nsub = 0;
     const bool sao = p.bEnableSAO != 0;
     std::vector<x265amd_sao_ctu> sparams((size_t)nctu);
     memset(sparams.data(), 0, sizeof(x265amd_sao_ctu) * nctu);
@@ -802,19 +792,9 @@ int x265amd_encoder::runFrameParallel(const PicP& picp)
     /* the rows' priority among the row tasks of all pictures in flight: the picture's place in coding order */
     const uint64_t rowOrder = pic.codingOrder + 1;
     const XaRowHooks hooks{ &gate, gateRowReady, gateBeforeRow, gateAfterRow, gateCtuWait, gateBeforeCtu, gateAfterCtu, gateRefWait, rowOrder, gateCtuReach };
-    XaTuRecs tuRecs = { nullptr, { nullptr, nullptr } };
-    if (p.limitTU >= 3)
-    {
-        /* (the records were sized when the picture was prepared: pictures coded beside this one read them CTU by CTU behind the gate) */
-        tuRecs.cur = pic.tuRecs.data();
-        for (int l = 0; l < 2; l++) if (!lists[l].empty() && lists[l][0]->tuRecs.size() == pic.tuRecs.size()) tuRecs.ref[l] = lists[l][0]->tuRecs.data();
-    }
-    x265amd_rskip_edge edge = { nullptr, 0, 0.0f };
-    const bool useEdge = p.recursionSkipMode == 2;
-    if (useEdge && fc.si.slice_type != 2) { const int erc = edgeCounts(pic, st, edge); if (erc != X265AMD_OK) { pic.fail(); filters.join(); return rc = erc; } }
-    int arc = xa_analyse_frame(me, st, &fc.info, &fc.sp, &fc.si, &fc.ap, pic.units.data(), pic.motion.data(), colPic ? colPic->motion.data() : noCol.data(),
-                               refDepth.data(), refQp0.data(), fc.planes.data(), (int)(fc.planes.size() / 3), stride, cstride, stat.data(), coeff.data(), nullptr,
-                               sao ? nullptr : data.data(), data.size(), sizes.data(), &nsub, &hooks, useDqp ? pic.cuQp.data() : nullptr, p.limitTU >= 3 ? &tuRecs : nullptr, useEdge ? &edge : nullptr);
+    /* (--limit-tu 3 / 4: the records were sized when the picture was prepared: pictures coded beside this one read them CTU by CTU behind the gate) */
+    if (p.recursionSkipMode == 2 && fc.si.slice_type != 2) { const int erc = edgeCounts(pic, st, bufs.edge); if (erc != X265AMD_OK) { pic.fail(); filters.join(); return rc = erc; } }
+    int arc = xa_analyse_frame(analysisArgs(*this, pic, fc, bufs), st, bufs.coeff.data(), nullptr, sao ? nullptr : bufs.data.data(), bufs.data.size(), bufs.sizes.data(), &bufs.nsub, &hooks);
     if (arc != X265AMD_OK) pic.fail();
     filters.join();
     if (arc != X265AMD_OK) return rc = arc;
@@ -823,10 +803,10 @@ int x265amd_encoder::runFrameParallel(const PicP& picp)
     if (p.bEnablePsnr || p.bEnableSsim) { arc = measureQuality(pic, st); if (arc != X265AMD_OK) return rc = arc; }
     if (sao)
     {
-        arc = x265amd_encode_slice_data(&fc.si, pic.units.data(), coeff.data(), sparams.data(), saoFlags, data.data(), data.size(), sizes.data(), &nsub);
+        arc = x265amd_encode_slice_data(&fc.si, pic.units.data(), bufs.coeff.data(), sparams.data(), saoFlags, bufs.data.data(), bufs.data.size(), bufs.sizes.data(), &bufs.nsub);
         if (arc != X265AMD_OK) return rc = arc;
     }
-    arc = sliceNal(*this, pic, fc, saoFlags, data, sizes, nsub);
+    arc = sliceNal(*this, pic, fc, saoFlags, bufs.data, bufs.sizes, bufs.nsub);
     if (arc) return rc = arc;
     if (!keepSources()) { xa_scratch_free(pic.dSrc); pic.dSrc = nullptr; }
     return rc = 0;

@@ -295,7 +295,7 @@ XA_DEV int chain_merge_candidates(const XaChainJob& J, int px, int py, int size,
     return count;
 }
 
-/* what the prediction of a candidate reads of its reference pictures, against what they have published (ctu_analysis.hip: xa_ref_guard_mc; encoder_api.hip:
+/* what the prediction of a candidate reads of its reference pictures, against what they have published (motion_map.hip: xa_ref_guard_mc; encoder_api.hip:
  * gateRefWait / gateCtuWait) */
 XA_DEV bool chain_reach_ok(const XaChainJob& J, int x, int y, int size, const ChainCand& c)
 {

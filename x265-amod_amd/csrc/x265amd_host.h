@@ -97,7 +97,7 @@ void xa_prof_dependency_wait(uint64_t ns);        /* X265AMD_QUEUE_PROF: time a 
 struct XaRects { uint64_t dst[4], src[4]; int16_t dst_stride[4], src_stride[4], w[4], h[4]; int32_t n; };         /* up to four; strides < 32768 samples */
 void xa_copy_rects(void* st, const XaRects& r);
 
-/* x265amd_analyse_frame with row hooks for pictures coded in parallel (csrc/ctu_analysis.hip; used by the encoder object): row_ready(ctx, row) says whether
+/* x265amd_analyse_frame with row hooks for pictures coded in parallel (csrc/frame_analysis.hip; used by the encoder object): row_ready(ctx, row) says whether
  * the reference pictures have finished the rows CTU row `row` may read (1 yes, 0 not yet, -1 a reference picture failed; polled, no blocking, no side
  * effects), before_row(ctx, row) runs once before the row's first CTU, after_row(ctx, row) once the row is analysed and its reconstruction is in device
  * memory.  Rows finish in order. */
@@ -120,27 +120,40 @@ struct XaRowHooks
      * vector goes through ref_wait on the host */
     void (*ctu_reach)(void* ctx, int row, int col, int* r0, int* r1, int* need);
 };
-/* device-resident mirrors of motion fields (csrc/ctu_analysis.hip; inter_chain_dev.h): one per host field, written by the host through the BAR as CUs are decided
+/* device-resident mirrors of motion fields (csrc/motion_map.hip; inter_chain_dev.h): one per host field, written by the host through the BAR as CUs are decided
  * and by the device's skip chain; NULL when device job queues are off */
 void* xa_devmap_register(const x265amd_mv_unit* host, size_t units);
 void xa_devmap_unregister(const x265amd_mv_unit* host);
 void* xa_devmap_find(const x265amd_mv_unit* host);
 void xa_devmap_push_rows(const x265amd_mv_unit* host, const x265amd_cu_unit* units, int w4, int y4a, int y4b);
-/* the guards (csrc/ctu_analysis.hip): wait until the row task's hooks (if it has any) let the jobs' reference samples be read; 0, or -1 when a picture failed */
+/* the guards (csrc/motion_map.hip): wait until the row task's hooks (if it has any) let the jobs' reference samples be read; 0, or -1 when a picture failed */
 int xa_ref_guard_mc(const x265amd_mc_job* jobs, int n);
 int xa_ref_guard_me(const x265amd_me_job* jobs, const int* pics, int n);
 /* --limit-tu 3 / 4: CUData::m_refTuDepth of every CTU (21 values each: the CUs of depth 0, 1 and 2 in raster order inside a depth; -1: nothing decided there) -- this picture's,
  * written as CUs are decided and read from the CTUs to the left and above, and those of the first reference picture of each list (read at the co-located CTU, which is coded
  * by then: the CTU gate) */
 struct XaTuRecs { int8_t* cur; const int8_t* ref[2]; };
-int xa_analyse_frame(x265amd_me_ctx* me, void* stream, const x265amd_mvpred_info* I, const x265amd_inter_search_params* S,
-                     const x265amd_slice_info* si, const x265amd_analysis_params* A, x265amd_cu_unit* units, x265amd_mv_unit* cur,
-                     const x265amd_mv_unit* col, const uint8_t* ref_depth, const int8_t* ref_qp0, const uint64_t* h_planes, int num_pics,
-                     intptr_t stride, intptr_t cstride, x265amd_cu_stat* cu_stat, int16_t* coeff_out, x265amd_ctu_result* results,
-                     uint8_t* slice_data, size_t cap, uint32_t* substream_sizes, int* num_substreams, const XaRowHooks* hooks, const int8_t* cu_qp = nullptr,
-                     const XaTuRecs* tu_recs = nullptr, const x265amd_rskip_edge* edge = nullptr);
-/* cu_qp (with si->use_dqp): Analysis::calculateQpforCuSize for every quantisation group, per CTU in z order -- 1 value (max_cu_dqp_depth 0) or 1 + 4 (depth 1): the QP of the
+/* The picture being analysed: what is the same for every CTU of it.  The members up to cu_stat are the arguments of those names of x265amd_analyse_frame and
+ * x265amd_compress_ctu_inter (include/x265amd.h); the last three are NULL where the configuration does not ask for them.
+ * cu_qp (with si->use_dqp): Analysis::calculateQpforCuSize for every quantisation group, per CTU in z order -- 1 value (max_cu_dqp_depth 0) or 1 + 4 (depth 1): the QP of the
  * 64x64 CU, then of its four 32x32 CUs; the encoder object fills it from the rate control's QP and the adaptive quantisation / cuTree offsets of the picture */
+struct XaAnalysisArgs
+{
+    x265amd_me_ctx* me; const x265amd_mvpred_info* I; const x265amd_inter_search_params* S; const x265amd_slice_info* si; const x265amd_analysis_params* A;
+    x265amd_cu_unit* units; x265amd_mv_unit* cur; const x265amd_mv_unit* col;
+    const uint8_t* ref_depth; const int8_t* ref_qp0;
+    const uint64_t* h_planes; int num_pics; intptr_t stride, cstride;
+    x265amd_cu_stat* cu_stat;
+    const int8_t* cu_qp; const XaTuRecs* tu_recs; const x265amd_rskip_edge* edge;
+};
+const int kTileElems = 4096 + 2048;        /* a CTU's levels: luma, then the two chroma planes (CUData::m_trCoeff layout) */
+/* the frame loop (csrc/frame_analysis.hip); hooks: NULL for a picture coded on its own */
+int xa_analyse_frame(const XaAnalysisArgs& pic, void* stream, int16_t* coeff_out, x265amd_ctu_result* results, uint8_t* slice_data, size_t cap,
+                     uint32_t* substream_sizes, int* num_substreams, const XaRowHooks* hooks);
+/* one CTU of it (csrc/ctu_analysis.hip: x265amd_compress_ctu_inter with the motion fields' device mirrors, NULL without) */
+struct XaMapUnit;
+int xa_compress_ctu(const XaAnalysisArgs& pic, void* stream, int ctu_addr, const uint8_t* ctx_in, uint64_t frac_in, int16_t* coeff_out, x265amd_ctu_result* out,
+                    XaMapUnit* dCur, const XaMapUnit* dCol);
 
 /* x265amd_check_intra / x265amd_intra_in_inter with a working set the caller keeps between the CUs of one CTU (csrc/intra_rd.hip): *ws starts as NULL */
 int xa_check_intra_ws(void* stream, const x265amd_slice_info* si, const x265amd_rd_params* rp, x265amd_cu_unit* units, const uint64_t* h_src, const uint64_t* h_rec,

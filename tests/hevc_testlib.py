@@ -1618,9 +1618,10 @@ _PU_RECTS = {0: [(0, 0, 4, 4)], 1: [(0, 0, 4, 2), (0, 2, 4, 2)], 2: [(0, 0, 2, 4
              4: [(0, 0, 4, 1), (0, 1, 4, 3)], 5: [(0, 0, 4, 3), (0, 3, 4, 1)], 6: [(0, 0, 1, 4), (1, 0, 3, 4)], 7: [(0, 0, 3, 4), (3, 0, 1, 4)]}
 
 
-def deblock_case(depth, seed, width, height, slice_b=True, bypass=False):
+def deblock_case(depth, seed, width, height, slice_b=True, bypass=False, qp_range=(18, 46)):
     """a random coding quad-tree over a width x height picture (multiples of 8): returns dict with padded planes, the raster
-    records for the reference driver (REF_DB_UNIT_DT) and for the oracle / product (DB_UNIT_DT), and the PPS offsets"""
+    records for the reference driver (REF_DB_UNIT_DT) and for the oracle / product (DB_UNIT_DT), and the PPS offsets.  qp_range: the half-open range the
+    QP of a CU is drawn from (the default is what every committed digest was made with; tests/test_filter_edges.py asks for the whole 0 .. 51)"""
     rng = np.random.default_rng(seed)
     dt = np.uint8 if depth == 8 else np.uint16
     pmax = (1 << depth) - 1
@@ -1647,7 +1648,7 @@ def deblock_case(depth, seed, width, height, slice_b=True, bypass=False):
             part = 3 if (size == 8 and rng.integers(0, 2)) else 0
         else:
             part = int(rng.choice([0, 0, 1, 2] + ([4, 5, 6, 7] if size >= 16 else [])))
-        qp = int(rng.integers(18, 46))
+        qp = int(rng.integers(*qp_range))
         byp = int(bypass and rng.integers(0, 6) == 0)
         ys, xs = slice(y // 4, (y + size) // 4), slice(x // 4, (x + size) // 4)
         ru["log2CU"][ys, xs] = log2; ru["partSize"][ys, xs] = part; ru["intra"][ys, xs] = intra; ru["qp"][ys, xs] = qp; ru["bypass"][ys, xs] = byp
@@ -5084,6 +5085,415 @@ def filter_case_expected(O, P, c):
         sh = 1 if k else 0
         O.lib.orc_extend_pic_border(off(f.reshape(-1), c["org"][1 if k else 0]), C.c_int64(c["cstride"] if k else c["stride"]), w >> sh, h >> sh, mx >> sh, my >> sh)
     return dict(D=D, count=cnt, org=org, params=params, F=F)
+
+
+# ---- the in-loop filter kernels at partial CTUs and parameter extremes (tests/test_filter_edges.py) ----
+# every partial extent from 8 to 56 in both directions on 2x2 CTUs, three CTU columns with a 24-sample tail, pictures smaller than a CTU
+EDGE_GEOMETRIES_2X2 = ((72, 120), (80, 112), (88, 104), (96, 96), (104, 88), (112, 80), (120, 72))
+EDGE_GEOMETRIES = EDGE_GEOMETRIES_2X2 + ((152, 24),) + ((8, 8), (16, 8), (8, 16), (24, 40), (40, 24), (56, 56), (64, 8), (8, 64))
+DB_TC_TABLE = (0,) * 18 + (1,) * 9 + (2,) * 4 + (3,) * 4 + (4,) * 3 + (5, 5, 6, 6, 7, 8, 9, 10, 11, 13, 14, 16, 18, 20, 22, 24)       # H.265 table 8-12
+assert len(DB_TC_TABLE) == 54
+
+
+def edge_poison(depth):
+    return 0xA5 if depth == 8 else 0x2A5
+
+
+def edge_frame(depth, width, height, pics):
+    """three picture-sized arrays (Y, U, V) laid into planes with the encoder's margins, the margins poisoned with a valid sample value: (planes, stride, cstride, org)"""
+    dt = np.uint8 if depth == 8 else np.uint16
+    mx, my = FILTER_MARGIN
+    stride, cstride = width + 2 * mx, width // 2 + mx
+    planes = []
+    for k, pic in enumerate(pics):
+        sh = 1 if k else 0
+        assert pic.shape == (height >> sh, width >> sh) and pic.min() >= 0 and pic.max() < (1 << depth)
+        full = np.full(((height >> sh) + 2 * (my >> sh), cstride if k else stride), edge_poison(depth), dt)
+        full[my >> sh:(my + height) >> sh, mx >> sh:(mx + width) >> sh] = pic
+        planes.append(full)
+    return planes, stride, cstride, (my * stride + mx, (my // 2) * cstride + mx // 2)
+
+
+def edge_picture(planes, width, height, k):
+    """the picture area of padded plane k"""
+    mx, my = FILTER_MARGIN
+    sh = 1 if k else 0
+    return planes[k][my >> sh:(my + height) >> sh, mx >> sh:(mx + width) >> sh]
+
+
+def edge_margins_intact(depth, planes, width, height, what):
+    """nothing outside the picture was written: the margins still hold the poison"""
+    for k, p in enumerate(planes):
+        m = p != edge_poison(depth)
+        edge_picture([m] * 3, width, height, k)[:] = False
+        if m.any():
+            ys, xs = np.nonzero(m)
+            raise AssertionError("%s: plane %d: %d margin samples written, first at x %d y %d: %d" % (
+                what, k, len(ys), xs[0] - (FILTER_MARGIN[0] >> (1 if k else 0)), ys[0] - (FILTER_MARGIN[1] >> (1 if k else 0)), p[ys[0], xs[0]]))
+
+
+def edge_first_diff(got, want, k):
+    """for an assertion message: where two padded planes first differ, in picture coordinates"""
+    ys, xs = np.nonzero(got != want)
+    sh = 1 if k else 0
+    return "plane %d: first of %d at x %d y %d: %d, want %d" % (k, len(ys), xs[0] - (FILTER_MARGIN[0] >> sh), ys[0] - (FILTER_MARGIN[1] >> sh), got[ys[0], xs[0]], want[ys[0], xs[0]])
+
+
+def edge_content(depth, rng, width, height, mode, qp_range=(18, 46), tc_offset=0):
+    """three picture-sized int64 arrays:
+    blocky    -- deblock_case's: 8x8 blocks in the middle third of the range with small noise;
+    saturated -- 8x8 blocks at levels from {0 .. 3} or {pmax - 3 .. pmax} (the range end chosen per 24x24 area, so most edges lie between nearly equal levels at one
+                 end), noise of +-1 << (depth - 8): filter results and offset sums reach and would pass 0 and pmax;
+    saturated_rough -- the same with noise of every integer up to +-3 << (depth - 8).  With +-1 at 8 bits the normal and chroma filters' sums only reach the ends of the
+                 range: a sample at pmax moves up only if the second sample behind the edge lies three (chroma: four) below the second before it, and the sample next
+                 to it then cannot be at pmax as well when a block spans two levels;
+    stepped   -- level = a walk along x plus a walk along y over the 8x8 grid, so every edge of a grid column (row) sees the same step: tc, 5 tc / 2, 10 tc or 27 tc (+-1) for
+                 the tc of a QP drawn from qp_range.  For flat sides the normal filter's delta is (6 step + 8) >> 4: the strong / normal decision turns at a step of
+                 5 tc / 2, the clip of delta at 8 tc / 3, the cut abs(delta) < 10 tc at 80 tc / 3.  Noise of every integer up to an amplitude drawn per block from
+                 1 .. 6 << (depth - 8): the second differences then reach 4 to 24 << (depth - 8) a line, so the activity of an edge falls on both sides of beta, beta / 4,
+                 beta / 8 and 3 beta / 16 at every QP up to beta's last entry, and at 10 bits not only on multiples of four;
+    noise     -- smoothed uniform noise (sao_case's);
+    flat      -- one level per plane;
+    checker   -- a one-sample checkerboard between two levels: local minima and maxima only."""
+    pmax, scale = (1 << depth) - 1, 1 << (depth - 8)
+    out = []
+    for k in range(3):
+        w, h = (width >> 1, height >> 1) if k else (width, height)
+        bw, bh = (w + 7) // 8, (h + 7) // 8
+        up = lambda lv, n=8: np.kron(lv, np.ones((n, n), np.int64))
+        if mode == "blocky":
+            p = up(rng.integers(0, pmax + 1, (bh, bw)))[:h, :w] // 3 + pmax // 3 + rng.integers(-2, 3, (h, w)) * scale
+        elif mode in ("saturated", "saturated_rough"):
+            high = up(rng.integers(0, 2, ((bh + 2) // 3, (bw + 2) // 3)), 3)[:bh, :bw]
+            lv = rng.integers(0, 4, (bh, bw))
+            noise = rng.integers(-1, 2, (h, w)) * scale if mode == "saturated" else rng.integers(-3 * scale, 3 * scale + 1, (h, w))
+            p = up(np.where(high == 1, pmax - lv, lv))[:h, :w] + noise
+        elif mode == "stepped":
+            def walk(n):
+                v, pos = np.zeros(n, np.int64), 0
+                for i in range(1, n):
+                    tc = DB_TC_TABLE[min(53, max(0, int(rng.integers(*qp_range)) + tc_offset))] * scale
+                    sign = 1 if rng.integers(0, 2) else -1
+                    for mult in rng.permutation(4):
+                        step = (tc, (5 * tc) // 2, 10 * tc, 27 * tc)[mult] + int(rng.integers(-1, 2)) * scale
+                        for s in (sign, -sign):
+                            if abs(pos + s * step) <= pmax // 4:
+                                break
+                        else:
+                            continue
+                        pos += s * step
+                        break
+                    v[i] = pos
+                return v
+            amp = up(rng.integers(1, 7, (bh, bw)))[:h, :w] * scale
+            p = pmax // 2 + up(walk(bw)[None, :] + walk(bh)[:, None])[:h, :w] + rng.integers(-amp, amp + 1)
+        elif mode == "noise":
+            full = rng.integers(0, pmax + 1, (h, w))
+            p = (full + np.roll(full, 1, 0) + np.roll(full, 1, 1) + np.roll(full, -1, 0)) // 4
+            if rng.integers(0, 2):
+                p = (p // 8) * 8 + rng.integers(0, 3, p.shape)
+        elif mode == "flat":
+            p = np.full((h, w), int(rng.integers(0, pmax + 1)), np.int64)
+        elif mode == "checker":
+            lo = int(rng.integers(0, pmax))
+            hi = int(rng.integers(lo + 1, pmax + 1))
+            yy, xx = np.mgrid[0:h, 0:w]
+            p = np.where((xx + yy) & 1, hi, lo)
+        else:
+            raise ValueError(mode)
+        out.append(np.clip(p, 0, pmax).astype(np.int64))
+    return out
+
+
+def deblock_edge_case(depth, seed, width, height, slice_b=True, bypass=False, qp_range=(18, 46), content="blocky", offsets=None):
+    """deblock_case's coding tree and records (QP per CU from qp_range) under planes with the encoder's margins, poisoned; the picture's content by edge_content from a
+    generator of its own; offsets: (beta / 2, tc / 2, Cb, Cr) of the PPS instead of deblock_case's draw from the narrow ranges"""
+    c = deblock_case(depth, seed, width, height, slice_b=slice_b, bypass=bypass, qp_range=qp_range)
+    if offsets is not None:
+        c["beta"], c["tc"], c["cb"], c["cr"] = offsets
+    rng = np.random.default_rng(seed + 424242)
+    planes, stride, cstride, org = edge_frame(depth, width, height, edge_content(depth, rng, width, height, content, qp_range, 2 * c["tc"]))
+    return dict(c, planes=planes, stride=stride, cstride=cstride, org=org, content=content, depth=depth)
+
+
+def deblock_index_clips(c):
+    """how often the table indices of the edges between an intra unit and its left or upper neighbour (strength 2 whatever the motion) leave their ranges, from QP + offset:
+    dict(beta_lo, beta_hi, tc_lo, tc_hi: luma; cqp_hi: the min(qp - 6, 51) of the chroma QP mapping fired, ctc_lo, ctc_hi: the chroma tc index)"""
+    w4, h4 = c["width"] // 4, c["height"] // 4
+    u = c["units"].reshape(h4, w4)
+    n = dict(beta_lo=0, beta_hi=0, tc_lo=0, tc_hi=0, cqp_hi=0, ctc_lo=0, ctc_hi=0)
+    for d, (tu, dy, dx) in enumerate(((DB_TU_LEFT, 0, 1), (DB_TU_TOP, 1, 0))):
+        for y4 in range(2 * dy, h4, 1 + dy):
+            for x4 in range(2 * dx, w4, 1 + dx):
+                q, p = u[y4, x4], u[y4 - dy, x4 - dx]
+                if not (q["flags"] & tu) or not ((q["flags"] | p["flags"]) & DB_INTRA) or (c["bypass"] and (q["flags"] & p["flags"] & DB_BYPASS)):
+                    continue
+                qp = (int(p["qp"]) + int(q["qp"]) + 1) >> 1
+                b, t = qp + 2 * c["beta"], qp + 2 + 2 * c["tc"]
+                n["beta_lo"] += b < 0; n["beta_hi"] += b > 51; n["tc_lo"] += t < 0; n["tc_hi"] += t > 53
+                across, along = (x4, y4) if d == 0 else (y4, x4)
+                if across & 3 or along & 1:
+                    continue
+                for o in (c["cb"], c["cr"]):
+                    cq = qp + o
+                    n["cqp_hi"] += cq - 6 > 51
+                    cq = cq if cq < 30 else ((29, 30, 31, 32, 33, 33, 34, 34, 35, 35, 36, 36, 37, 37)[cq - 30] if cq < 44 else min(cq - 6, 51))
+                    n["ctc_lo"] += cq + 2 + 2 * c["tc"] < 0; n["ctc_hi"] += cq + 2 + 2 * c["tc"] > 53
+    return n
+
+
+def deblock_strength_rows():
+    """the boundary-strength table of H.265 8.7.2.4 as (what, edge kind, unit P, unit Q, strength): 'tu' -- P and Q are 8x8 CUs without further split, the edge between
+    them a transform edge; 'pu' -- the two prediction units of one 16x16 CU with a single transform unit.  Picture identities per list, vectors in quarter samples."""
+    A, B, Z = (8, -4), (-5, 9), (0, 0)
+    U = lambda ref=(0, 1), mv=(A, B), intra=0, cbf=0: dict(ref=ref, mv=mv, intra=intra, cbf=cbf)
+    add = lambda v, d: (v[0] + d[0], v[1] + d[1])
+    rows = []
+    for lst in (0, 1):
+        for axis in (0, 1):
+            for dist, bs in ((3, 0), (4, 1)):
+                d = (dist, 0) if axis == 0 else (0, -dist)
+                rows.append(("same pictures in the same order, list %d differs by %d in %s" % (lst, dist, "xy"[axis]), "tu", U(), U(mv=(add(A, d), B) if lst == 0 else (A, add(B, d))), bs))
+    one = lambda mv: U(ref=(2, 2), mv=mv)
+    rows += [
+        ("swapped lists, crosswise 3 apart, straight far", "tu", U(), U(ref=(1, 0), mv=(add(B, (3, 0)), add(A, (0, -3)))), 0),
+        ("swapped lists, crosswise 4 apart in y on one list", "tu", U(), U(ref=(1, 0), mv=(add(B, (0, 4)), A)), 1),
+        ("swapped lists, crosswise far, straight 3 apart", "tu", U(), U(ref=(1, 0), mv=(add(A, (3, 0)), add(B, (0, 3)))), 1),
+        ("one picture on both lists, straight near, crosswise near", "tu", one(((8, -4), (9, -3))), one(((10, -3), (8, -2))), 0),
+        ("one picture on both lists, straight near, crosswise far", "tu", one((A, B)), one((add(A, (3, 0)), add(B, (0, -3)))), 0),
+        ("one picture on both lists, straight far, crosswise near", "tu", one((A, B)), one((add(B, (3, 0)), add(A, (0, 3)))), 0),
+        ("one picture on both lists, straight far (4 on list 0), crosswise far", "tu", one((A, B)), one((add(A, (4, 0)), B)), 1),
+        ("uni-predicted P, bi-predicted Q, list 0 equal", "tu", U(ref=(0, -1), mv=(A, Z)), U(), 1),
+        ("bi-predicted P, uni-predicted Q, list 1 equal", "tu", U(), U(ref=(-1, 1), mv=(Z, B)), 1),
+        ("different pictures, equal vectors", "tu", U(ref=(0, -1), mv=(A, Z)), U(ref=(1, -1), mv=(A, Z)), 1),
+        ("list 0 alone, same picture, 3 apart", "tu", U(ref=(0, -1), mv=(A, Z)), U(ref=(0, -1), mv=(add(A, (-3, 3)), Z)), 0),
+        ("list 0 alone, same picture, 4 apart", "tu", U(ref=(0, -1), mv=(A, Z)), U(ref=(0, -1), mv=(add(A, (-4, 0)), Z)), 1),
+        ("one picture, list 0 in P and list 1 in Q, 3 apart", "tu", U(ref=(0, -1), mv=(A, Z)), U(ref=(-1, 0), mv=(Z, add(A, (0, 3)))), 0),
+        ("one picture, list 0 in P and list 1 in Q, 4 apart", "tu", U(ref=(0, -1), mv=(A, Z)), U(ref=(-1, 0), mv=(Z, add(A, (0, 4)))), 1),
+        ("intra P", "tu", U(ref=(-1, -1), mv=(Z, Z), intra=1), U(), 2),
+        ("intra Q", "tu", U(), U(ref=(-1, -1), mv=(Z, Z), intra=1), 2),
+        ("coded residual in P, transform edge, equal motion", "tu", U(cbf=1), U(), 1),
+        ("coded residual in Q, transform edge, equal motion", "tu", U(), U(cbf=1), 1),
+        ("no residual, transform edge, equal motion", "tu", U(), U(), 0),
+        ("coded residual, prediction edge alone, equal motion", "pu", U(cbf=1), U(cbf=1), 0),
+        ("coded residual, prediction edge alone, 4 apart", "pu", U(cbf=1), U(cbf=1, mv=(A, add(B, (4, 0)))), 1),
+        ("no residual, prediction edge alone, different pictures", "pu", U(), U(ref=(0, 2)), 1),
+    ]
+    return rows
+
+
+def deblock_strength_case(depth):
+    """every row of deblock_strength_rows once on a vertical and once on a horizontal edge: one 16x16 slot per (row, direction) in a 128-wide B picture, QP 40, no offsets.
+    Flat 8x8 blocks whose level alternates by six (<< depth - 8): an edge of strength 1 or 2 changes the two samples next to it (beta 42, tc 6 or 7: d = 0, the strong
+    filter moves a step of six), an edge of strength 0 nothing.  Returns deblock_case's dict plus `edges`: (what, direction, x, y of the slot, strength)."""
+    rows = deblock_strength_rows()
+    width = 128
+    height = (2 * len(rows) + 7) // 8 * 16
+    w4, h4 = width // 4, height // 4
+    ru = np.zeros((h4, w4), REF_DB_UNIT_DT)
+    du = np.zeros((h4, w4), DB_UNIT_DT)
+    ru["qp"] = 40; du["qp"] = 40
+
+    def put_cu(x, y, size, part, pus):
+        ys, xs = slice(y // 4, (y + size) // 4), slice(x // 4, (x + size) // 4)
+        ru["log2CU"][ys, xs] = int(np.log2(size)); ru["partSize"][ys, xs] = part; ru["intra"][ys, xs] = pus[0]["intra"]; ru["cbf"][ys, xs] = pus[0]["cbf"]
+        du["flags"][ys, xs] |= pus[0]["intra"] * DB_INTRA + pus[0]["cbf"] * DB_CBF
+        du["flags"][ys, x // 4] |= DB_TU_LEFT
+        du["flags"][y // 4, xs] |= DB_TU_TOP
+        q = size // 4
+        for u, (px, py, pw, ph) in zip(pus, _PU_RECTS[part]):
+            pys, pxs = slice((y + py * q) // 4, (y + (py + ph) * q) // 4), slice((x + px * q) // 4, (x + (px + pw) * q) // 4)
+            for arr in (ru, du):
+                arr["ref"][pys, pxs] = u["ref"]; arr["mv"][pys, pxs] = u["mv"]
+            if px:
+                du["flags"][pys, (x + px * q) // 4] |= DB_PU_LEFT
+            if py:
+                du["flags"][(y + py * q) // 4, pxs] |= DB_PU_TOP
+
+    edges = []
+    filler = dict(ref=(0, 1), mv=((8, -4), (-5, 9)), intra=0, cbf=0)
+    for slot in range((width // 16) * (height // 16)):
+        x, y = slot % (width // 16) * 16, slot // (width // 16) * 16
+        if slot >= 2 * len(rows):
+            for k in range(4):
+                put_cu(x + (k & 1) * 8, y + (k >> 1) * 8, 8, 0, [filler])
+            continue
+        what, kind, P, Q, bs = rows[slot // 2]
+        d = slot & 1
+        if kind == "pu":
+            put_cu(x, y, 16, 1 if d else 2, [P, Q])
+        else:
+            for k in range(4):
+                put_cu(x + (k & 1) * 8, y + (k >> 1) * 8, 8, 0, [Q if (k >> 1 if d else k & 1) else P])
+        edges.append((what, d, x, y, bs))
+    yy, xx = np.mgrid[0:height // 8, 0:width // 8]
+    step = 6 << (depth - 8)
+    luma = np.kron((1 << (depth - 1)) + step * ((xx + yy) & 1), np.ones((8, 8), np.int64))
+    yy, xx = np.mgrid[0:height // 16, 0:width // 16]
+    chroma = np.kron((1 << (depth - 1)) + step * ((xx + yy) & 1), np.ones((8, 8), np.int64))
+    planes, stride, cstride, org = edge_frame(depth, width, height, [luma, chroma, chroma.copy()])
+    return dict(planes=planes, stride=stride, cstride=cstride, org=org, width=width, height=height, ref_units=np.ascontiguousarray(ru.ravel()),
+                units=np.ascontiguousarray(du.ravel()), beta=0, tc=0, cb=0, cr=0, bypass=0, slice_p=0, edges=edges, depth=depth)
+
+
+def deblock_strength_changed(c, before, after):
+    """per entry of c['edges']: did the two luma samples next to the slot's inner edge change, on the lines that edges of the other direction never touch (3 and 4 of an
+    8x8 block)"""
+    a, b = edge_picture(before, c["width"], c["height"], 0), edge_picture(after, c["width"], c["height"], 0)
+    out = []
+    for (what, d, x, y, bs) in c["edges"]:
+        lines = [y + 3, y + 4, y + 11, y + 12] if d == 0 else [x + 3, x + 4, x + 11, x + 12]
+        if d == 0:
+            ch = [bool((a[l, x + 7:x + 9] != b[l, x + 7:x + 9]).all()) for l in lines]
+        else:
+            ch = [bool((a[y + 7:y + 9, l] != b[y + 7:y + 9, l]).all()) for l in lines]
+        same = [bool((a[l, x + 5:x + 11] == b[l, x + 5:x + 11]).all()) if d == 0 else bool((a[y + 5:y + 11, l] == b[y + 5:y + 11, l]).all()) for l in lines]
+        assert all(ch) or all(same), (what, d, ch, same)
+        out.append(all(ch))
+    return out
+
+
+def _dev_planes(planes, org, shift=0):
+    """the padded planes on the device, `shift` samples into buffers one sample longer (poison in front); the table of the picture origins' addresses"""
+    import torch
+    isz = planes[0].itemsize
+    bufs = []
+    for p in planes:
+        flat = np.concatenate([p.ravel()[:1]] * shift + [p.ravel()])
+        bufs.append(torch.from_numpy(flat.view(np.uint8).copy()).cuda())
+    tab = np.array([b.data_ptr() + (o + shift) * isz for b, o in zip(bufs, (org[0], org[1], org[1]))], np.uint64)
+    return bufs, tab
+
+
+def _host_planes(bufs, planes, shift=0):
+    return [b.cpu().numpy().view(p.dtype)[shift:].reshape(p.shape) for b, p in zip(bufs, planes)]
+
+
+def deblock_run_hip_forms(L, c, passes=3):
+    """the picture through x265amd_deblock_picture, through x265amd_deblock_rows CTU row by CTU row, and through x265amd_deblock_rows_cols CTU row by CTU row and column
+    by column in order: dict(picture, rows, cols) of padded planes.  passes 1 or 2: that pass alone in every form."""
+    import torch
+    w, h = c["width"], c["height"]
+    d_units = torch.from_numpy(c["units"].view(np.uint8).copy()).cuda()
+    tail = (C.c_void_p(d_units.data_ptr()), c["beta"], c["tc"], c["cb"], c["cr"], c["bypass"], passes)
+    out = {}
+    for form in ("picture", "rows", "cols"):
+        bufs, tab = _dev_planes(c["planes"], c["org"])
+        head = (None, C.c_void_p(int(tab[0])), C.c_void_p(int(tab[1])), C.c_void_p(int(tab[2])), C.c_int64(c["stride"]), C.c_int64(c["cstride"]), w, h)
+        if form == "picture":
+            assert L.lib.x265amd_deblock_picture(*head, *tail) == 0
+        else:
+            for y4 in range(0, h // 4, 16):
+                y4e = min(h // 4, y4 + 16)
+                if form == "rows":
+                    assert L.lib.x265amd_deblock_rows(*head, *tail, y4, y4e) == 0
+                else:
+                    for col in range((w + 63) // 64):
+                        assert L.lib.x265amd_deblock_rows_cols(*head, *tail, y4, y4e, col, col + 1) == 0
+        torch.cuda.synchronize()
+        out[form] = _host_planes(bufs, c["planes"])
+    return out
+
+
+def sao_edge_case(depth, seed, width, height, content="noise", source="near", force_band=None, index=0):
+    """sao_case's record under planes with the encoder's margins, poisoned (source picture included).  content: edge_content's mode of the deblocked picture; source:
+    'near' -- the picture plus noise of +-6, 'opposite' -- the other end of the range (pmax - sample: the largest differences the sums can hold).  Parameters: offsets from
+    the whole range (+-7 at 8 bits, +-31 at 10) with both ends put into every CTU's luma record, the types of CTU j cycling through -1 .. 4 from `index` on, luma and chroma
+    at different rates; force_band: the band positions of CTU j's three planes become force_band[(j + plane) % len]"""
+    rng = np.random.default_rng(seed)
+    pmax = (1 << depth) - 1
+    rec = edge_content(depth, rng, width, height, content)
+    if source == "near":
+        fenc = [np.clip(r + rng.integers(-6, 7, r.shape), 0, pmax) for r in rec]
+    else:
+        fenc = [pmax - r for r in rec]
+    planes, stride, cstride, org = edge_frame(depth, width, height, rec)
+    fplanes = edge_frame(depth, width, height, fenc)[0]
+    nctu = ((width + 63) // 64) * ((height + 63) // 64)
+    top = 7 if depth == 8 else 31
+    params = np.zeros(nctu, SAO_CTU_DT)
+    params["bandPos"] = rng.integers(0, 32, (nctu, 3))
+    params["offset"] = rng.integers(-top, top + 1, (nctu, 3, 4))
+    for j in range(nctu):
+        n = 4 * index + j
+        params["type"][j] = (n % 6 - 1, (n + n // 6 + 2) % 6 - 1)
+        for plane in range(3):
+            params["offset"][j, plane, (j + plane) % 4] = top if (j + plane) & 1 else -top
+            if force_band:
+                params["bandPos"][j, plane] = force_band[(j + plane) % len(force_band)]
+    return dict(rec=planes, fenc=fplanes, stride=stride, cstride=cstride, org=org, width=width, height=height, params=params, nctu=nctu, depth=depth, content=content)
+
+
+def sao_apply_coverage(c):
+    """from the deblocked picture and the parameters: dict(clip_lo, clip_hi: samples whose offset sum leaves the range, wrapped: samples of a band pos + k > 31 with a
+    non-zero offset) -- the edge offsets' sums computed with the table of H.265 8.7.3"""
+    w, h = c["width"], c["height"]
+    pmax = (1 << c["depth"]) - 1
+    ctuW = (w + 63) // 64
+    n = dict(clip_lo=0, clip_hi=0, wrapped=0)
+    for k in range(3):
+        sh = 1 if k else 0
+        v = edge_picture(c["rec"], w, h, k).astype(np.int64)
+        ph, pw = v.shape
+        yy, xx = np.mgrid[0:ph, 0:pw]
+        ctu = ((yy << sh) >> 6) * ctuW + ((xx << sh) >> 6)
+        typ = c["params"]["type"][:, 1 if k else 0].astype(np.int64)[ctu]
+        offs = c["params"]["offset"][:, k, :].astype(np.int64)[ctu]                      # [y][x][4]
+        pos = c["params"]["bandPos"][:, k].astype(np.int64)[ctu]
+        out = v.copy()
+        band = ((v >> (c["depth"] - 5)) - pos) & 31
+        isb = (typ == 4) & (band < 4)
+        boff = np.take_along_axis(offs, np.minimum(band, 3)[..., None], 2)[..., 0]
+        out[isb] += boff[isb]
+        n["wrapped"] += int((isb & (pos + band > 31) & (boff != 0)).sum())
+        e = np.pad(v, 1, mode="edge")
+        for t, (dx, dy) in enumerate(((-1, 0), (0, -1), (-1, -1), (1, -1))):
+            a, b = e[1 + dy:1 + dy + ph, 1 + dx:1 + dx + pw], e[1 - dy:1 - dy + ph, 1 - dx:1 - dx + pw]
+            cls = np.array([1, 2, 0, 3, 4])[np.sign(v - a) + np.sign(v - b) + 2]
+            inside = np.ones_like(v, bool)
+            if dx:
+                inside[:, 0] = inside[:, -1] = False
+            if dy:
+                inside[0, :] = inside[-1, :] = False
+            m = (typ == t) & inside & (cls > 0)
+            eoff = np.take_along_axis(offs, np.maximum(cls - 1, 0)[..., None], 2)[..., 0]
+            out[m] += eoff[m]
+        n["clip_lo"] += int((out < 0).sum()); n["clip_hi"] += int((out > pmax).sum())
+    return n
+
+
+def sao_run_hip_forms(L, c):
+    """dict: picture -- (count, offsetOrg, offset planes) through x265amd_sao_stats / x265amd_sao_apply; cols -- the same through x265amd_sao_stats_rows_cols CTU by CTU
+    and x265amd_sao_apply_rows_cols CTU row by CTU row and 64-sample column range by range, in order; odd -- (count, offsetOrg) through x265amd_sao_stats with every
+    plane's origin one sample further into its buffer"""
+    import torch
+    w, h = c["width"], c["height"]
+    ctuW, ctuH = (w + 63) // 64, (h + 63) // 64
+    n = c["nctu"] * 3 * 5 * 32
+    geom = (C.c_int64(c["stride"]), C.c_int64(c["cstride"]), w, h)
+    d_par = torch.from_numpy(c["params"].view(np.uint8).copy()).cuda()
+    out = {}
+    for form in ("picture", "cols", "odd"):
+        shift = 1 if form == "odd" else 0
+        rec, rtab = _dev_planes(c["rec"], c["org"], shift)
+        fenc, ftab = _dev_planes(c["fenc"], c["org"], shift)
+        dst, dtab = _dev_planes(c["rec"], c["org"], shift)
+        d_cnt = torch.full((n,), -1515870811, dtype=torch.int32, device="cuda"); d_org = torch.full((n,), -1515870811, dtype=torch.int32, device="cuda")
+        stats = (None, _ptr(rtab), _ptr(ftab), *geom, C.c_void_p(d_cnt.data_ptr()), C.c_void_p(d_org.data_ptr()))
+        apply = (None, _ptr(rtab), _ptr(dtab), *geom, C.c_void_p(d_par.data_ptr()))
+        if form == "cols":
+            for r in range(ctuH):
+                for col in range(ctuW):
+                    assert L.lib.x265amd_sao_stats_rows_cols(*stats, r, r + 1, col, col + 1) == 0
+                for col in range(ctuW):
+                    assert L.lib.x265amd_sao_apply_rows_cols(*apply, r, r + 1, 64 * col, min(w, 64 * col + 64)) == 0
+        else:
+            assert L.lib.x265amd_sao_stats(*stats) == 0
+            if form == "picture":
+                assert L.lib.x265amd_sao_apply(*apply) == 0
+        torch.cuda.synchronize()
+        out[form] = (d_cnt.cpu().numpy(), d_org.cpu().numpy(), _host_planes(dst, c["rec"], shift), _host_planes(rec, c["rec"], shift))
+    return out
 
 
 # ----------------------------------------------------------------------------------------------------------

@@ -657,7 +657,7 @@ int x265amd_deblock_units_rows(const x265amd_slice_info* si, const x265amd_mvpre
 int x265amd_deblock_units_rect(const x265amd_slice_info* si, const x265amd_mvpred_info* info, const x265amd_cu_unit* units, const x265amd_mv_unit* motion,
                                x265amd_deblock_unit* out, int y4_begin, int y4_end, int x4_begin, int x4_end);
 
-/* --- sample adaptive offset over a picture, the two data-parallel halves; 4:2:0, sao-non-deblock off.
+/* --- sample adaptive offset over a picture, the two data-parallel halves; 4:2:0 (the forms of sao-non-deblock and limit-sao: further down).
  * Plane tables are HOST arrays of 3 device addresses (sample (0,0) of Y, U, V).
  * x265amd_sao_stats = SAO::calcSaoStatsCTU for every CTU and plane (reference: source/encoder/sao.cpp:735-917 with
  * saoCuStatsBO/E0..E3 :1762-1925): d_count / d_offset_org[((ctu * 3 + plane) * 5 + type) * 32 + class], type 0..3 = EO_0..3
@@ -689,6 +689,27 @@ int x265amd_sao_stats_rows_cols(void* stream, const uint64_t rec_planes[3], cons
                                 int width, int height, int32_t* d_count, int32_t* d_offset_org, int ctu_row_begin, int ctu_row_end, int ctu_col_begin, int ctu_col_end);
 int x265amd_sao_apply_rows_cols(void* stream, const uint64_t src_planes[3], const uint64_t dst_planes[3], intptr_t stride, intptr_t cstride,
                                 int width, int height, const x265amd_sao_ctu* d_params, int ctu_row_begin, int ctu_row_end, int x_begin, int x_end);
+/* The statistics under --sao-non-deblock and --limit-sao.  flags: X265AMD_SAO_NON_DEBLOCK = calcSaoStatsCTU's skips with param.bSaoNonDeblocked (sao.cpp:812-896:
+ * lines / columns left out at the bottom / right of a CTU: BO 3 / 4, EO_0 3 / 5, EO_1 4 / 4, EO_2 and EO_3 4 / 5; without it 4 / 5 for every type);
+ * X265AMD_SAO_EO01_ONLY = a B picture under param.bLimitSAO (sao.cpp:861): EO_2 and EO_3 are not measured and their words are zero.  flags 0 = the calls above.
+ * x265amd_sao_stats_pre = SAO::calcSaoStatsCu_BeforeDblk (sao.cpp:919-1197): the statistics of those right and bottom strips on the reconstruction BEFORE any
+ * deblocking (rec_planes; it reads the CTU rows themselves and one line above them), same layout; the decision adds the two records (sao.cpp:1251-1255). */
+enum { X265AMD_SAO_NON_DEBLOCK = 1, X265AMD_SAO_EO01_ONLY = 2 };
+int x265amd_sao_stats_opt(void* stream, const uint64_t rec_planes[3], const uint64_t fenc_planes[3], intptr_t stride, intptr_t cstride,
+                          int width, int height, int32_t* d_count, int32_t* d_offset_org, int flags);
+int x265amd_sao_stats_opt_rows(void* stream, const uint64_t rec_planes[3], const uint64_t fenc_planes[3], intptr_t stride, intptr_t cstride,
+                               int width, int height, int32_t* d_count, int32_t* d_offset_org, int flags, int ctu_row_begin, int ctu_row_end);
+int x265amd_sao_stats_opt_rows_cols(void* stream, const uint64_t rec_planes[3], const uint64_t fenc_planes[3], intptr_t stride, intptr_t cstride,
+                                    int width, int height, int32_t* d_count, int32_t* d_offset_org, int flags, int ctu_row_begin, int ctu_row_end, int ctu_col_begin, int ctu_col_end);
+int x265amd_sao_stats_pre(void* stream, const uint64_t rec_planes[3], const uint64_t fenc_planes[3], intptr_t stride, intptr_t cstride,
+                          int width, int height, int32_t* d_pre_count, int32_t* d_pre_offset_org);
+int x265amd_sao_stats_pre_rows(void* stream, const uint64_t rec_planes[3], const uint64_t fenc_planes[3], intptr_t stride, intptr_t cstride,
+                               int width, int height, int32_t* d_pre_count, int32_t* d_pre_offset_org, int ctu_row_begin, int ctu_row_end);
+/* The same statistics on the host, sample by sample (host/sao_stats_model.cpp): what the kernels are compared with.  Planes are HOST pointers to sample (0,0) of Y, U, V
+ * (the library's pixel type); pre_planes = the reconstruction before deblocking, read only when pre_count / pre_offset_org are given (both or neither); count /
+ * offset_org may be NULL when only the pre-deblock record is wanted.  Every word of the arrays given is written (nctu * 3 * 5 * 32 each). */
+int x265amd_sao_stats_model(const void* const rec_planes[3], const void* const fenc_planes[3], const void* const pre_planes[3], intptr_t stride, intptr_t cstride,
+                            int width, int height, int flags, int32_t* pre_count, int32_t* pre_offset_org, int32_t* count, int32_t* offset_org);
 
 /* --- the column forms' schedule (host code, host/filter_plan.cpp): which column chunks of which CTU rows the filter thread of a picture takes next while the
  * picture's analysis still advances, and which samples are final behind them.  A chunk [col_begin, col_end) of CTU row `row` is taken in two steps.
@@ -1078,7 +1099,7 @@ int x265amd_encode_slice_data(const x265amd_slice_info* si, x265amd_cu_unit* uni
  * source/encoder/sao.cpp:227-272, :1207-1761) on the statistics of x265amd_sao_stats (host copies, same layout).  referenced: IS_REFERENCED(frame);
  * frame_threads: param.frameNumThreads (the automatic switch-off of startSlice only runs when 1); qp_min / qp_max: param.rc.qpMin / qpMax.
  * depth_sao_rate: 8 doubles kept across the pictures of an encode (SAO::m_depthSaoRate), zero at the start.  params: per CTU (reserved[0] =
- * merge mode); sao_flags[2]: slice_sao_luma_flag, slice_sao_chroma_flag.  limit-sao and sao-non-deblock are not supported. */
+ * merge mode); sao_flags[2]: slice_sao_luma_flag, slice_sao_chroma_flag.  Without limit-sao and sao-non-deblock: these calls are the _opt forms below with zeros. */
 int x265amd_sao_rdo(const x265amd_slice_info* si, int referenced, int frame_threads, int qp_min, int qp_max, x265amd_cu_unit* units,
                     const int32_t* count, const int32_t* offset_org, double* depth_sao_rate, x265amd_sao_ctu* params, int32_t* sao_flags);
 /* CTU rows ctu_row_begin .. ctu_row_end - 1 of the same decision (rows in order; frame_threads > 1 unless the call covers the picture) */
@@ -1090,6 +1111,21 @@ int x265amd_sao_rdo_rows(const x265amd_slice_info* si, int referenced, int frame
 int x265amd_sao_rdo_cols(const x265amd_slice_info* si, int referenced, int frame_threads, int qp_min, int qp_max, x265amd_cu_unit* units,
                          const int32_t* count, const int32_t* offset_org, x265amd_sao_ctu* params, int32_t* sao_flags,
                          int ctu_row, int ctu_col_begin, int ctu_col_end, uint8_t* carry);
+/* The same three decisions under --limit-sao and --sao-non-deblock.  flags: the X265AMD_SAO_* word the statistics were made with.  limit_sao: param.bLimitSAO
+ * (sao.cpp:1276-1309, :1384-1392, :1496-1504, :1626-1640): in B slices, and in CTUs of P slices whose first unit is skipped, the edge types tried are EO_0 and EO_1
+ * alone; in a B slice a CTU that is skipped or whose merge candidates are all off (none at all counts as off) is not decided -- no luma statistics, no luma decision --
+ * and chroma is decided only where luma was decided and came out on; the merge candidates are priced all the same, on what the CTU's statistics then hold.
+ * pre_count / pre_offset_org: the record of x265amd_sao_stats_pre (NULL, NULL without X265AMD_SAO_NON_DEBLOCK; both with it): what the statistics of every CTU and
+ * plane start from (sao.cpp:1251-1255) -- and all they hold where limit_sao leaves a plane's own statistics out. */
+int x265amd_sao_rdo_opt(const x265amd_slice_info* si, int referenced, int frame_threads, int qp_min, int qp_max, x265amd_cu_unit* units,
+                        const int32_t* count, const int32_t* offset_org, double* depth_sao_rate, x265amd_sao_ctu* params, int32_t* sao_flags,
+                        int flags, int limit_sao, const int32_t* pre_count, const int32_t* pre_offset_org);
+int x265amd_sao_rdo_rows_opt(const x265amd_slice_info* si, int referenced, int frame_threads, int qp_min, int qp_max, x265amd_cu_unit* units,
+                             const int32_t* count, const int32_t* offset_org, double* depth_sao_rate, x265amd_sao_ctu* params, int32_t* sao_flags,
+                             int ctu_row_begin, int ctu_row_end, int flags, int limit_sao, const int32_t* pre_count, const int32_t* pre_offset_org);
+int x265amd_sao_rdo_cols_opt(const x265amd_slice_info* si, int referenced, int frame_threads, int qp_min, int qp_max, x265amd_cu_unit* units,
+                             const int32_t* count, const int32_t* offset_org, x265amd_sao_ctu* params, int32_t* sao_flags,
+                             int ctu_row, int ctu_col_begin, int ctu_col_end, uint8_t* carry, int flags, int limit_sao, const int32_t* pre_count, const int32_t* pre_offset_org);
 
 /* --- lookahead lowres pipeline, first stage.
  * x265amd_lowres_init = Lowres::init (reference: source/common/lowres.cpp:337-403): frame_init_lowres_core (source/common/pixel.cpp:605-628) from the

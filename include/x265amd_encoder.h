@@ -171,6 +171,25 @@ typedef struct x265amd_picture                                                  
 
 typedef struct x265amd_encoder x265amd_encoder;
 x265amd_encoder* x265amd_encoder_open(const x265amd_param* p);
+/* x265amd_param is full (the ctypes mirrors of its callers have exactly its size): options built after it go into an extension record handed over beside it.
+ * The three SAO options, under Encoder::configure's rules (encoder.cpp:3789-3796, :4009-4011), restated by the open call in this order: selectiveSAO != 0 switches
+ * bEnableSAO on; bEnableSAO with selectiveSAO 0 makes it 4; bSaoNonDeblocked and bLimitSAO are cleared without bEnableSAO.  None of them with shardCount > 1.
+ *   selectiveSAO (--selective-sao; Encoder::encode, encoder.cpp:2343-2364): which pictures are offset at all -- 1 the I pictures, 2 everything but B slices (when
+ *     bframes != 0), 3 the pictures other pictures reference, 4 every picture.  A picture left out is coded as --no-sao codes it, its slice header says
+ *     slice_sao_luma_flag = slice_sao_chroma_flag = 0 (entropy.cpp:647-658); the SPS flag stays bEnableSAO.
+ *   bLimitSAO (--limit-sao; sao.cpp:861, :1276-1309, :1384-1392, :1496-1504, :1626-1640): in B slices and in skipped CTUs of P slices only EO_0, EO_1 and BO are
+ *     tried; in B slices a CTU that is skipped, or whose merge candidates are all off, is not decided at all, and chroma only where luma came out on.
+ *   bSaoNonDeblocked (--sao-non-deblock; sao.cpp:812-896, :919-1197, :1251-1255): a CTU's statistics reach further to the right and down (x265amd_sao_stats_opt) and
+ *     start from the statistics of its right and bottom strips before deblocking (x265amd_sao_stats_pre), gathered between a row's analysis and the first deblocking
+ *     that could touch what they read.  With pictures coded in parallel such a picture's filters run row by row. */
+typedef struct x265amd_param_ext {
+    uint32_t size;              /* sizeof(x265amd_param_ext) as the caller knows it; fields beyond it read as 0 */
+    int32_t bSaoNonDeblocked;   /* param.bSaoNonDeblocked (--sao-non-deblock; 0) */
+    int32_t bLimitSAO;          /* param.bLimitSAO (--limit-sao; 0) */
+    int32_t selectiveSAO;       /* param.selectiveSAO (--selective-sao 0..4; 0) */
+    int32_t reserved[12];       /* zero */
+} x265amd_param_ext;
+x265amd_encoder* x265amd_encoder_open_ext(const x265amd_param* p, const x265amd_param_ext* ext);   /* ext == NULL: x265amd_encoder_open(p) */
 /* VPS, SPS, PPS; the array and payloads stay valid until the next call on this encoder.  Returns the total payload size or -1. */
 int x265amd_encoder_headers(x265amd_encoder* enc, x265amd_nal** pp_nal, uint32_t* pi_nal);
 /* pic_in == NULL flushes.  Returns 1 when a coded picture was emitted (its NAL units in *pp_nal, its reconstruction copied to

@@ -7,7 +7,8 @@
  *     x265amd --input clip.y4m -o out.hevc [--preset|-p name] [--tune|-t name] [--recon|-r rec.yuv|rec.y4m] [--frames|-f N] [--csv log.csv] [any option x265_param_parse knows:
  *             --crf F --qp N --aq-mode N --aq-strength F --[no-]cutree --qcomp F --qg-size N --bframes N --b-adapt N --[no-]b-pyramid --[no-]open-gop --keyint N --min-keyint N
  *             --scenecut N --no-scenecut --[no-]hist-scenecut --rc-lookahead N --lookahead-slices N --ref N --limit-refs N --rd N --rdoq-level N --psy-rd F --psy-rdoq F --me name --subme N
- *             --merange N --max-merge N --[no-]rect --[no-]amp --[no-]limit-modes --[no-]early-skip --rskip N (0, 1, 2) --rskip-edge-threshold N --[no-]weightp --[no-]weightb --[no-]sao --[no-]deblock --[no-]wpp
+ *             --merange N --max-merge N --[no-]rect --[no-]amp --[no-]limit-modes --[no-]early-skip --rskip N (0, 1, 2) --rskip-edge-threshold N --[no-]weightp --[no-]weightb --[no-]sao --[no-]sao-non-deblock --[no-]limit-sao
+ *             --selective-sao N (0..4) --[no-]deblock --[no-]wpp
  *             --tu-intra-depth N --tu-inter-depth N --[no-]signhide --[no-]strong-intra-smoothing --[no-]temporal-mvp --[no-]b-intra --[no-]fast-intra --[no-]info --[no-]psnr --[no-]ssim --max-cll C,F
  *             --frame-threads N --pools S --min-luma N --max-luma N ...] [-D|--output-depth 8|10] [--dither]
  *

@@ -77,9 +77,22 @@ void x265amd_encoder::fillStreamParams(x265amd_stream_params& s) const
     s.beta_offset_div2 = p.deblockingFilterBetaOffset; s.tc_offset_div2 = p.deblockingFilterTCOffset;
 }
 
-extern "C" x265amd_encoder* x265amd_encoder_open(const x265amd_param* p)
+extern "C" x265amd_encoder* x265amd_encoder_open(const x265amd_param* p) { return x265amd_encoder_open_ext(p, nullptr); }
+
+extern "C" x265amd_encoder* x265amd_encoder_open_ext(const x265amd_param* p, const x265amd_param_ext* extIn)
 {
     if (!p) { xa_fail(X265AMD_EINVAL, "encoder_open: null param"); return nullptr; }
+    /* the extension record as far as the caller knows it: what lies beyond its size reads as zero; a record longer than this library's could name options it does not know */
+    x265amd_param_ext ext;
+    memset(&ext, 0, sizeof(ext));
+    if (extIn)
+    {
+        if (extIn->size < sizeof(uint32_t) || (extIn->size & 3) || extIn->size > sizeof(ext)) { xa_fail(X265AMD_EINVAL, "encoder_open: x265amd_param_ext.size (a multiple of 4 up to sizeof(x265amd_param_ext))"); return nullptr; }
+        memcpy(&ext, extIn, extIn->size);
+        for (int32_t r : ext.reserved) if (r) { xa_fail(X265AMD_EINVAL, "encoder_open: x265amd_param_ext.reserved must be zero"); return nullptr; }
+        /* x265_check_params (param.cpp:1833), before any rule below */
+        if (ext.selectiveSAO < 0 || ext.selectiveSAO > 4) { xa_fail(X265AMD_EINVAL, "encoder_open: selectiveSAO outside 0..4"); return nullptr; }
+    }
     /* Encoder::configure's rules for the rate control's switches (encoder.cpp:3721-3754): constant QP switches adaptive quantisation and cuTree off; cuTree without AQ gets
      * aq-mode 1 at strength 0 (cuTree needs the offset arrays; delta QP is on); strength 0 without cuTree is no AQ at all */
     x265amd_param norm = *p;
@@ -93,6 +106,11 @@ extern "C" x265amd_encoder* x265amd_encoder_open(const x265amd_param* p)
     }
     /* the HDR10 SEI units come with the parameter sets at every keyframe ("Turning on repeat-headers for HDR compatibility", encoder.cpp:4347-4353) */
     if (norm.bEmitHDR10SEI || norm.hasMasteringDisplay || norm.maxCLL || norm.maxFALL) { norm.bEmitHDR10SEI = 1; norm.bRepeatHeaders = 1; }
+    /* Encoder::configure (encoder.cpp:3789-3796, :4009-4011), in its order */
+    if (ext.selectiveSAO && !norm.bEnableSAO) norm.bEnableSAO = 1;               /* "SAO turned ON when selective-sao is ON" */
+    if (!ext.selectiveSAO && norm.bEnableSAO) ext.selectiveSAO = 4;
+    ext.bSaoNonDeblocked = ext.bSaoNonDeblocked && norm.bEnableSAO;
+    ext.bLimitSAO = ext.bLimitSAO && norm.bEnableSAO;
     if (norm.limitTU && norm.tuQTMaxInterDepth < 2) norm.limitTU = 0;          /* "limit-tu disabled, requires tu-inter-depth > 1" (encoder.cpp:4103-4107) */
     if (norm.rateControlMode != X265AMD_RC_CRF) { norm.aqMode = 0; norm.cuTree = 0; }
     if (norm.lookaheadDepth == 0) norm.cuTree = 0;
@@ -153,6 +171,9 @@ extern "C" x265amd_encoder* x265amd_encoder_open(const x265amd_param* p)
         /* the quality metrics are measured by the object that codes a picture and summed by the one that hands it out: no test runs several ranks */
         XA_REQUIRE(!p->bEnablePsnr || p->shardCount <= 1, "bEnablePsnr with pictures coded on several GPUs (shardCount > 1) is not built");
         XA_REQUIRE(!p->bEnableSsim || p->shardCount <= 1, "bEnableSsim with pictures coded on several GPUs (shardCount > 1) is not built");
+        /* the SAO options: the pre-deblock record and the per-picture switch are the coding object's own; no test runs several ranks */
+        XA_REQUIRE(!(ext.bSaoNonDeblocked || ext.bLimitSAO || (ext.selectiveSAO && ext.selectiveSAO != 4)) || p->shardCount <= 1,
+                   "bSaoNonDeblocked / bLimitSAO / selectiveSAO with pictures coded on several GPUs (shardCount > 1) is not built");
         XA_REQUIRE(p->limitReferences >= 0 && p->limitReferences <= 3, "limitReferences outside 0..3");
         XA_REQUIRE(!p->bEnableAMP || p->bEnableRectInter, "bEnableAMP needs bEnableRectInter");
 #undef XA_REQUIRE
@@ -161,6 +182,7 @@ extern "C" x265amd_encoder* x265amd_encoder_open(const x265amd_param* p)
     xa_bind_device();           /* the threads of this library work on the opening thread's GPU */
     std::unique_ptr<x265amd_encoder> e(new x265amd_encoder);
     e->p = *p;
+    e->selectiveSAO = ext.selectiveSAO; e->limitSAO = ext.bLimitSAO != 0; e->saoNonDeblock = ext.bSaoNonDeblocked != 0;
     /* a size that is no multiple of the smallest CU is coded padded to one, the pad replicating the last column / row, and the SPS's conformance window takes it off again
      * (Encoder::configure, encoder.cpp:4081-4090, :4300-4308; PicYuv::copyFromPicture) */
     e->srcW = p->sourceWidth; e->srcH = p->sourceHeight;
@@ -280,6 +302,8 @@ extern "C" x265amd_encoder* x265amd_encoder_open(const x265amd_param* p)
         hipMalloc((void**)&e->dDbUnits, sizeof(x265amd_deblock_unit) * e->w4 * e->h4) != hipSuccess ||
         xa_scratch_alloc((void**)&e->dSaoTmp, e->picElems * sizeof(pixel)) != hipSuccess)
     { xa_fail(X265AMD_EHIP, "encoder_open: device allocation"); return nullptr; }
+    if (e->saoNonDeblock && (hipMalloc((void**)&e->dSaoPreCount, nstat * 4) != hipSuccess || hipMalloc((void**)&e->dSaoPreOrg, nstat * 4) != hipSuccess))
+    { xa_fail(X265AMD_EHIP, "encoder_open: device allocation"); return nullptr; }
     x265amd_stream_params sp;
     e->fillStreamParams(sp);
     e->headerBytes.resize(512);
@@ -314,13 +338,14 @@ extern "C" x265amd_encoder* x265amd_encoder_open(const x265amd_param* p)
         snprintf(text, sizeof(text), "x265amd (x265 build 209 interface) - %s - H.265/HEVC codec on AMD Instinct MI355X - options: %dx%d fps=%u/%u bitdepth=%d %s=%g aq-mode=%d aq-strength=%.2f "
                  "cutree=%d qcomp=%.2f qg-size=%d bframes=%d b-adapt=%d b-pyramid=%d open-gop=%d keyint=%d min-keyint=%d scenecut=%d rc-lookahead=%d lookahead-slices=%d ref=%d limit-refs=%d "
                  "rd=%d rdoq-level=%d psy-rd=%.2f me=%d subme=%d merange=%d max-merge=%d rect=%d amp=%d limit-modes=%d early-skip=%d rskip=%d weightp=%d weightb=%d sao=%d deblock=%d wpp=%d "
-                 "tu-intra-depth=%d tu-inter-depth=%d signhide=%d strong-intra-smoothing=%d temporal-mvp=%d b-intra=%d fast-intra=%d",
+                 "tu-intra-depth=%d tu-inter-depth=%d signhide=%d strong-intra-smoothing=%d temporal-mvp=%d b-intra=%d fast-intra=%d sao-non-deblock=%d selective-sao=%d limit-sao=%d",
                  x265amd_version(), p->sourceWidth, p->sourceHeight, p->fpsNum, p->fpsDenom, X265AMD_DEPTH, p->rateControlMode == X265AMD_RC_CRF ? "crf" : "qp",
                  p->rateControlMode == X265AMD_RC_CRF ? p->rfConstant : (double)p->qp, e->aqOn ? p->aqMode : 0, p->aqStrength, p->cuTree != 0, p->qCompress, p->qgSize, p->bframes, p->bFrameAdaptive,
                  p->bBPyramid != 0, p->bOpenGOP != 0, p->keyframeMax, e->keyframeMin, p->scenecutThreshold, p->lookaheadDepth, p->lookaheadSlices, p->maxNumReferences, p->limitReferences,
                  p->rdLevel, p->rdoqLevel, p->psyRd, p->searchMethod, p->subpelRefine, p->searchRange, p->maxNumMergeCand, p->bEnableRectInter != 0, p->bEnableAMP != 0, p->limitModes != 0,
                  p->bEnableEarlySkip != 0, p->recursionSkipMode, p->bEnableWeightedPred != 0, p->bEnableWeightedBiPred != 0, p->bEnableSAO != 0, p->bEnableLoopFilter != 0, p->bEnableWavefront != 0,
-                 p->tuQTMaxIntraDepth, p->tuQTMaxInterDepth, p->bEnableSignHiding != 0, p->bEnableStrongIntraSmoothing != 0, p->bEnableTemporalMvp != 0, p->bIntraInBFrames != 0, p->bEnableFastIntra != 0);
+                 p->tuQTMaxIntraDepth, p->tuQTMaxInterDepth, p->bEnableSignHiding != 0, p->bEnableStrongIntraSmoothing != 0, p->bEnableTemporalMvp != 0, p->bIntraInBFrames != 0, p->bEnableFastIntra != 0,
+                 e->saoNonDeblock, e->selectiveSAO, e->limitSAO);
         uint8_t sei[1400];
         const size_t m = x265amd_write_info_sei(text, sei, sizeof(sei));
         if (!m) { xa_fail(X265AMD_EINVAL, "encoder_open: info SEI"); return nullptr; }
@@ -693,6 +718,13 @@ static int encoder_encode_impl(x265amd_encoder* e, x265amd_nal** ppNal, uint32_t
             PicP pic = e->ready.front();
             e->ready.pop_front();
             if (e->prepare(pic)) return -1;
+            /* --selective-sao: a picture that is not offset is final in dRec, as every picture is without SAO (its type is known from here on, and nobody has asked
+             * for its planes yet: the pictures that reference it are prepared behind it) */
+            if (pic->dFin && !e->picSao(*pic))
+            {
+                if (hipStreamSynchronize(nullptr) != hipSuccess) return -1;         /* the buffer was cleared on the null stream when the picture came in: long done */
+                xa_scratch_free(pic->dFin); pic->dFin = nullptr;
+            }
             pic->codingOrder = e->codingCount++;
             pic->owned = e->p.shardCount <= 1 || (int)(pic->codingOrder % (uint64_t)e->p.shardCount) == e->p.shardRank;
             e->inflight.push_back(pic);

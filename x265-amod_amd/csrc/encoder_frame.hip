@@ -106,7 +106,7 @@ static void frameContext(const x265amd_encoder& e, Pic& pic, FrameCtx& c)
     memset(&ap, 0, sizeof(ap));
     ap.psy_rd = p.psyRd; ap.rd_level = p.rdLevel; ap.early_skip = p.bEnableEarlySkip != 0; ap.rskip = p.recursionSkipMode; ap.limit_refs = p.limitReferences;
     ap.b_intra = p.bIntraInBFrames != 0; ap.rect = p.bEnableRectInter != 0; ap.amp = p.bEnableAMP != 0; ap.limit_modes = p.limitModes != 0;
-    ap.strong_intra_smoothing = p.bEnableStrongIntraSmoothing != 0; ap.use_sao = p.bEnableSAO != 0;
+    ap.strong_intra_smoothing = p.bEnableStrongIntraSmoothing != 0; ap.use_sao = e.picSao(pic);           /* per picture under --selective-sao (frameencoder.cpp:684-699 asks the slice) */
     ap.fast_intra = p.bEnableFastIntra != 0; ap.limit_tu = p.limitTU;
     ap.rdoq_level = p.rdoqLevel; ap.psy_rdoq_scale = p.rdoqLevel ? p.psyRdoqFix8 : 0;      /* encoder.cpp:3667: no psy-rdoq without RDOQ */
 }
@@ -126,7 +126,8 @@ static int sliceNal(const x265amd_encoder& e, Pic& pic, const FrameCtx& c, const
         for (const PicP& q : pic.pos) { h.delta_poc[j] = q->poc - pic.poc; h.used[j++] = pic.rpsUsed; }
     }
     h.temporal_mvp_enabled = p.bEnableTemporalMvp != 0;
-    h.use_sao = p.bEnableSAO != 0; h.sao_luma = saoFlags[0]; h.sao_chroma = saoFlags[1];
+    /* a picture --selective-sao leaves out says so with two zero flags (entropy.cpp:647-658); selectiveSAO is non-zero whenever the SPS says SAO */
+    h.use_sao = e.picSao(pic); h.selective_sao = e.selectiveSAO; h.sao_luma = saoFlags[0]; h.sao_chroma = saoFlags[1];
     h.num_ref_idx[0] = c.info.num_ref_idx[0]; h.num_ref_idx[1] = c.info.num_ref_idx[1]; h.num_ref_idx_default[0] = h.num_ref_idx_default[1] = 1;
     h.col_from_l0 = c.stype != 0; h.col_ref_idx = 0; h.max_num_merge_cand = p.maxNumMergeCand;
     h.slice_qp = pic.sliceQp; h.pps_init_qp = 26; h.deblocking_disabled = !p.bEnableLoopFilter;
@@ -260,7 +261,7 @@ int x265amd_encoder::runFrame(const PicP& picp, std::shared_future<int> prev)
             for (size_t i = 0; i < nUnits; i++) bufs.refDepth[l * nUnits + i] = q->units[i].depth;
             for (int i = 0; i < nctu; i++) bufs.refQp0[(size_t)l * nctu + i] = useDqp ? q->units[(size_t)(i / ctuW) * 16 * w4 + (size_t)(i % ctuW) * 16].qp : (int8_t)q->sliceQp;      /* CUData::m_qp[0] of the co-located CTU */
         }
-    const bool sao = p.bEnableSAO != 0;
+    const bool sao = picSao(pic);
     if (useDqp && pic.cuQp.empty()) return xa_fail(X265AMD_EINVAL, "encoder: the picture has no CU QPs");
     if (p.limitTU >= 3) pic.tuRecs.assign((size_t)nctu * 21, -1);
     if (p.recursionSkipMode == 2 && si.slice_type != 2) { const int erc = edgeCounts(pic, st, bufs.edge); if (erc != X265AMD_OK) return erc; }
@@ -271,6 +272,15 @@ int x265amd_encoder::runFrame(const PicP& picp, std::shared_future<int> prev)
     /* ---- from here on in coding order ---- */
     if (prev.valid() && prev.get() != 0) return X265AMD_EHIP;
     pixel* recY = pic.dRec + org[0]; pixel* recU = pic.dRec + org[1]; pixel* recV = pic.dRec + org[2];
+    const bool saoPre = sao && saoNonDeblock;
+    if (saoPre)
+    {
+        /* --sao-non-deblock: the statistics of every CTU's right and bottom strips while nothing is deblocked yet (SAO::calcSaoStatsCu_BeforeDblk, frameencoder.cpp:1599) */
+        const uint64_t recP[3] = { planeAddr(pic.dRec, 0), planeAddr(pic.dRec, 1), planeAddr(pic.dRec, 2) };
+        const uint64_t srcP[3] = { planeAddr(pic.dSrc, 0), planeAddr(pic.dSrc, 1), planeAddr(pic.dSrc, 2) };
+        rc = x265amd_sao_stats_pre(st, recP, srcP, stride, cstride, W, H, dSaoPreCount, dSaoPreOrg);
+        if (rc != X265AMD_OK) return rc;
+    }
     if (p.bEnableLoopFilter)
     {
         std::vector<x265amd_deblock_unit> dbu(nUnits);
@@ -289,16 +299,21 @@ int x265amd_encoder::runFrame(const PicP& picp, std::shared_future<int> prev)
         const uint64_t recP[3] = { planeAddr(pic.dRec, 0), planeAddr(pic.dRec, 1), planeAddr(pic.dRec, 2) };
         const uint64_t srcP[3] = { planeAddr(pic.dSrc, 0), planeAddr(pic.dSrc, 1), planeAddr(pic.dSrc, 2) };
         if (hipMemsetAsync(dSaoCount, 0, nstat * 4, st) != hipSuccess || hipMemsetAsync(dSaoOrg, 0, nstat * 4, st) != hipSuccess) return xa_fail(X265AMD_EHIP, "encoder: sao memset");
-        rc = x265amd_sao_stats(st, recP, srcP, stride, cstride, W, H, dSaoCount, dSaoOrg);
+        const int statFlags = saoStatFlags(pic);
+        rc = x265amd_sao_stats_opt(st, recP, srcP, stride, cstride, W, H, dSaoCount, dSaoOrg, statFlags);
         if (rc != X265AMD_OK) return rc;
-        std::vector<int32_t> cnt(nstat), orgs(nstat);
+        std::vector<int32_t> cnt(nstat), orgs(nstat), preCnt(saoPre ? nstat : 0), preOrgs(saoPre ? nstat : 0);
+        if (saoPre && (hipMemcpyAsync(preCnt.data(), dSaoPreCount, nstat * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+                       hipMemcpyAsync(preOrgs.data(), dSaoPreOrg, nstat * 4, hipMemcpyDeviceToHost, st) != hipSuccess))
+            return xa_fail(X265AMD_EHIP, "encoder: sao download");
         if (hipMemcpyAsync(cnt.data(), dSaoCount, nstat * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
             hipMemcpyAsync(orgs.data(), dSaoOrg, nstat * 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
             return xa_fail(X265AMD_EHIP, "encoder: sao download");
         std::vector<x265amd_sao_ctu> sparams((size_t)nctu);
         memset(sparams.data(), 0, sizeof(x265amd_sao_ctu) * nctu);
-        rc = x265amd_sao_rdo(&si, pic.type != TYPE_B ? 1 : 0, 1, p.qpMin, p.qpMax,       /* IS_REFERENCED: fixed by the type (hasReferences changes as later pictures are prepared) */
-                             pic.units.data(), cnt.data(), orgs.data(), depthSaoRate, sparams.data(), saoFlags);
+        rc = x265amd_sao_rdo_opt(&si, pic.type != TYPE_B ? 1 : 0, 1, p.qpMin, p.qpMax,       /* IS_REFERENCED: fixed by the type (hasReferences changes as later pictures are prepared) */
+                                 pic.units.data(), cnt.data(), orgs.data(), depthSaoRate, sparams.data(), saoFlags,
+                                 statFlags, limitSAO, saoPre ? preCnt.data() : nullptr, saoPre ? preOrgs.data() : nullptr);
         if (rc != X265AMD_OK) return rc;
         if (hipMemcpyAsync(dSaoParams, sparams.data(), sizeof(x265amd_sao_ctu) * nctu, hipMemcpyHostToDevice, st) != hipSuccess ||
             hipMemcpyAsync(dSaoTmp, pic.dRec, picElems * sizeof(pixel), hipMemcpyDeviceToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
@@ -490,17 +505,24 @@ int x265amd_encoder::filterRows(Pic& pic, const x265amd_slice_info& si, const x2
     hipStream_t st = nullptr;
     if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) return xa_fail(X265AMD_EHIP, "encoder: stream");
     struct StreamGuard { hipStream_t s; ~StreamGuard() { (void)hipStreamDestroy(s); } } guard{ st };
-    const bool sao = p.bEnableSAO != 0, dbl = p.bEnableLoopFilter != 0;
+    const bool sao = picSao(pic), dbl = p.bEnableLoopFilter != 0, saoPre = sao && saoNonDeblock;
+    const int statFlags = saoStatFlags(pic);
     const size_t nUnits = (size_t)w4 * h4, nstat = (size_t)nctu * 3 * 5 * 32, rowStat = (size_t)ctuW * 3 * 5 * 32;
-    struct Scratch { void* p = nullptr; ~Scratch() { xa_scratch_free(p); } } dDb, dCnt, dOrg, dPar;
+    struct Scratch { void* p = nullptr; ~Scratch() { xa_scratch_free(p); } } dDb, dCnt, dOrg, dPar, dPreCnt, dPreOrg;
     std::vector<x265amd_deblock_unit> dbu;
-    std::vector<int32_t> cnt, orgs;
+    std::vector<int32_t> cnt, orgs, preCnt, preOrgs;
+    int preRows = 0;            /* --sao-non-deblock: CTU rows whose pre-deblock statistics are enqueued */
     if (dbl) { if (xa_scratch_alloc(&dDb.p, sizeof(x265amd_deblock_unit) * nUnits) != hipSuccess) return xa_fail(X265AMD_EHIP, "encoder: device allocation"); dbu.resize(nUnits); }
     if (sao)
     {
         if (xa_scratch_alloc(&dCnt.p, nstat * 4) != hipSuccess || xa_scratch_alloc(&dOrg.p, nstat * 4) != hipSuccess || xa_scratch_alloc(&dPar.p, sizeof(x265amd_sao_ctu) * nctu) != hipSuccess)
             return xa_fail(X265AMD_EHIP, "encoder: device allocation");
         cnt.resize(nstat); orgs.resize(nstat);
+        if (saoPre)
+        {
+            if (xa_scratch_alloc(&dPreCnt.p, nstat * 4) != hipSuccess || xa_scratch_alloc(&dPreOrg.p, nstat * 4) != hipSuccess) return xa_fail(X265AMD_EHIP, "encoder: device allocation");
+            preCnt.resize(nstat); preOrgs.resize(nstat);
+        }
         saoFlags[0] = saoFlags[1] = 1;          /* SAO::startSlice: never switched off when pictures are coded in parallel (sao.cpp:264) */
     }
     pixel* recY = pic.dRec + org[0]; pixel* recU = pic.dRec + org[1]; pixel* recV = pic.dRec + org[2];
@@ -543,6 +565,16 @@ int x265amd_encoder::filterRows(Pic& pic, const x265amd_slice_info& si, const x2
         }
         stamp(0);
         const int y4b = r * 16, y4e = std::min(h4, y4b + 16);
+        if (saoPre && preRows <= std::min(r + 1, ctuH - 1))
+        {
+            /* --sao-non-deblock: the pre-deblock statistics of every analysed row that has not had them (rows <= r + 1 are analysed), on this stream in front of the
+             * deblocking of row r -- whose vertical edges change row r's last line, which the statistics of row r + 1 read, and whose top edge reaches up into row r - 1;
+             * they read their own rows and the last line of the row above, none of it deblocked yet.  Every word of the rows' records is stored: nothing to clear */
+            const int upTo = std::min(r + 1, ctuH - 1) + 1;
+            rc = x265amd_sao_stats_pre_rows(st, recP, srcP, stride, cstride, W, H, (int32_t*)dPreCnt.p, (int32_t*)dPreOrg.p, preRows, upTo);
+            if (rc != X265AMD_OK) break;
+            preRows = upTo;
+        }
         if (dbl)
         {
             rc = x265amd_deblock_units_rows(&si, &info, pic.units.data(), pic.motion.data(), dbu.data(), y4b, y4e);
@@ -558,14 +590,18 @@ int x265amd_encoder::filterRows(Pic& pic, const x265amd_slice_info& si, const x2
         {
             if (hipMemsetAsync((int32_t*)dCnt.p + r * rowStat, 0, rowStat * 4, st) != hipSuccess || hipMemsetAsync((int32_t*)dOrg.p + r * rowStat, 0, rowStat * 4, st) != hipSuccess)
             { rc = xa_fail(X265AMD_EHIP, "encoder: sao memset"); break; }
-            rc = x265amd_sao_stats_rows(st, recP, srcP, stride, cstride, W, H, (int32_t*)dCnt.p, (int32_t*)dOrg.p, r, r + 1);
+            rc = x265amd_sao_stats_opt_rows(st, recP, srcP, stride, cstride, W, H, (int32_t*)dCnt.p, (int32_t*)dOrg.p, statFlags, r, r + 1);
             if (rc != X265AMD_OK) break;
+            if (saoPre && (hipMemcpyAsync(preCnt.data() + r * rowStat, (int32_t*)dPreCnt.p + r * rowStat, rowStat * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+                           hipMemcpyAsync(preOrgs.data() + r * rowStat, (int32_t*)dPreOrg.p + r * rowStat, rowStat * 4, hipMemcpyDeviceToHost, st) != hipSuccess))
+            { rc = xa_fail(X265AMD_EHIP, "encoder: sao download"); break; }
             if (hipMemcpyAsync(cnt.data() + r * rowStat, (int32_t*)dCnt.p + r * rowStat, rowStat * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
                 hipMemcpyAsync(orgs.data() + r * rowStat, (int32_t*)dOrg.p + r * rowStat, rowStat * 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
             { rc = xa_fail(X265AMD_EHIP, "encoder: sao download"); break; }
             stamp(3);
             int32_t flags[2] = { 1, 1 };
-            rc = x265amd_sao_rdo_rows(&si, pic.type != TYPE_B ? 1 : 0, 2, p.qpMin, p.qpMax, pic.units.data(), cnt.data(), orgs.data(), unusedRate, sparams.data(), flags, r, r + 1);
+            rc = x265amd_sao_rdo_rows_opt(&si, pic.type != TYPE_B ? 1 : 0, 2, p.qpMin, p.qpMax, pic.units.data(), cnt.data(), orgs.data(), unusedRate, sparams.data(), flags, r, r + 1,
+                                          statFlags, limitSAO, saoPre ? preCnt.data() : nullptr, saoPre ? preOrgs.data() : nullptr);
             if (rc != X265AMD_OK) break;
             if (hipMemcpyAsync((x265amd_sao_ctu*)dPar.p + (size_t)r * ctuW, sparams.data() + (size_t)r * ctuW, sizeof(x265amd_sao_ctu) * ctuW, hipMemcpyHostToDevice, st) != hipSuccess ||
                 hipStreamSynchronize(st) != hipSuccess)
@@ -622,7 +658,8 @@ int x265amd_encoder::filterRowsCols(Pic& pic, const x265amd_slice_info& si, cons
     hipEvent_t ev = nullptr;
     (void)hipEventCreateWithFlags(&ev, hipEventDisableTiming);
     struct EventGuard { hipEvent_t e; ~EventGuard() { if (e) (void)hipEventDestroy(e); } } evGuard{ ev };
-    const bool sao = p.bEnableSAO != 0, dbl = p.bEnableLoopFilter != 0;
+    const bool sao = picSao(pic), dbl = p.bEnableLoopFilter != 0;
+    const int statFlags = saoStatFlags(pic);            /* (never X265AMD_SAO_NON_DEBLOCK here: those pictures take filterRows) */
     const size_t nUnits = (size_t)w4 * h4, ctuStat = (size_t)3 * 5 * 32, nstat = (size_t)nctu * ctuStat;
     /* deblocking records, SAO statistics and parameters: mapped memory the device reads / writes in place (no staging copies, no synchronisation to free a
      * staging buffer): the records as the host derives them, the statistics as the kernel stores them, the parameters as decided. */
@@ -718,7 +755,7 @@ int x265amd_encoder::filterRowsCols(Pic& pic, const x265amd_slice_info& si, cons
                 if (sao)
                 {
                     /* every workgroup stores all 160 sums and counts of its (CTU, plane): nothing to clear; the host reads them where the kernel leaves them */
-                    rc = x265amd_sao_stats_rows_cols(st, recP, srcP, stride, cstride, W, H, cnt, orgs, s.row, s.row + 1, s.col_begin, s.col_end);
+                    rc = x265amd_sao_stats_opt_rows_cols(st, recP, srcP, stride, cstride, W, H, cnt, orgs, statFlags, s.row, s.row + 1, s.col_begin, s.col_end);
                     if (rc != X265AMD_OK) break;
                 }
             }
@@ -734,8 +771,8 @@ int x265amd_encoder::filterRowsCols(Pic& pic, const x265amd_slice_info& si, cons
                 const x265amd_filter_step& u = steps[i];
                 if (u.kind != X265AMD_FILTER_FULL) continue;
                 int32_t flags[2] = { 1, 1 };
-                rc = x265amd_sao_rdo_cols(&si, pic.type != TYPE_B ? 1 : 0, 2, p.qpMin, p.qpMax, pic.units.data(), cnt, orgs, sparams.data(), flags, u.row, u.col_begin, u.col_end,
-                                          carry.data() + (size_t)u.row * (X265AMD_CTX_STRIDE + 8));
+                rc = x265amd_sao_rdo_cols_opt(&si, pic.type != TYPE_B ? 1 : 0, 2, p.qpMin, p.qpMax, pic.units.data(), cnt, orgs, sparams.data(), flags, u.row, u.col_begin, u.col_end,
+                                              carry.data() + (size_t)u.row * (X265AMD_CTX_STRIDE + 8), statFlags, limitSAO, nullptr, nullptr);
                 if (rc != X265AMD_OK) break;
                 const size_t off = (size_t)u.row * ctuW + u.col_begin, n = (size_t)(u.col_end - u.col_begin);
                 memcpy((x265amd_sao_ctu*)hPar.p + off, sparams.data() + off, sizeof(x265amd_sao_ctu) * n);
@@ -779,14 +816,15 @@ int x265amd_encoder::runFrameParallel(const PicP& picp)
         for (const PicP& q : lists[l]) if (std::find(gate.refs.begin(), gate.refs.end(), q.get()) == gate.refs.end()) gate.refs.push_back(q.get());
         if (!lists[l].empty()) for (int i = 0; i < nctu; i++) bufs.refQp0[(size_t)l * nctu + i] = (int8_t)lists[l][0]->sliceQp;
     }
-    const bool sao = p.bEnableSAO != 0;
+    const bool sao = picSao(pic);
     std::vector<x265amd_sao_ctu> sparams((size_t)nctu);
     memset(sparams.data(), 0, sizeof(x265amd_sao_ctu) * nctu);
     int32_t saoFlags[2] = { 0, 0 };
     int filterRc = X265AMD_OK;
     /* by columns when there is something to filter and the rows run as a wavefront; the row-by-row form otherwise */
     static const bool colsOff = !xa_env_on("X265AMD_FILTER_COLS");
-    const bool byCols = !colsOff && p.bEnableWavefront && (p.bEnableLoopFilter || p.bEnableSAO) && ctuH > 1 && ctuW > 1;
+    /* (a picture that gathers pre-deblock statistics, --sao-non-deblock, goes by rows: the pass is not fitted into the column sweeps) */
+    const bool byCols = !colsOff && p.bEnableWavefront && (p.bEnableLoopFilter || sao) && ctuH > 1 && ctuW > 1 && !(sao && saoNonDeblock);
     std::thread filters([&, byCols] { xa_thread_device(); filterRc = byCols ? filterRowsCols(pic, fc.si, fc.info, sparams, saoFlags) : filterRows(pic, fc.si, fc.info, sparams, saoFlags); if (filterRc) pic.fail();
                                       cpuFilterNs += thread_cpu_ns(); });
     /* the rows' priority among the row tasks of all pictures in flight: the picture's place in coding order */

@@ -219,6 +219,21 @@ struct x265amd_encoder
     std::vector<x265amd_nal> nals;
     std::vector<pixel> staging;
     pixel* uploadBuf = nullptr;         /* pinned: the padded input picture as uploadPicture puts it together (hipHostFree in the destructor) */
+    /* x265amd_param_ext as Encoder::configure's rules left it (x265amd_encoder_open_ext): selectiveSAO is 1..4 whenever p.bEnableSAO is set */
+    int selectiveSAO = 0; bool limitSAO = false, saoNonDeblock = false;
+    /* Encoder::encode's choice per picture (encoder.cpp:2343-2364): slice->m_bUseSao.  IS_REFERENCED is fixed by the type, as everywhere here */
+    bool picSao(const Pic& pic) const
+    {
+        if (!p.bEnableSAO) return false;
+        const bool sliceI = pic.type == TYPE_IDR || pic.type == TYPE_I;
+        if (selectiveSAO == 1) return sliceI;
+        if (selectiveSAO == 2) return !(p.bframes != 0 && isBType(pic.type));
+        if (selectiveSAO == 3) return pic.type != TYPE_B;
+        return true;
+    }
+    /* the X265AMD_SAO_* word of a picture's statistics: the non-deblock skips; no EO_2 / EO_3 in a B slice under --limit-sao (sao.cpp:861) */
+    int saoStatFlags(const Pic& pic) const { return (saoNonDeblock ? X265AMD_SAO_NON_DEBLOCK : 0) | (limitSAO && isBType(pic.type) ? X265AMD_SAO_EO01_ONLY : 0); }
+    int32_t* dSaoPreCount = nullptr; int32_t* dSaoPreOrg = nullptr;     /* --sao-non-deblock, one picture at a time: the pre-deblock record */
     int32_t* dSaoCount = nullptr; int32_t* dSaoOrg = nullptr; x265amd_sao_ctu* dSaoParams = nullptr; x265amd_deblock_unit* dDbUnits = nullptr;
     pixel* dSaoTmp = nullptr;
 
@@ -237,6 +252,8 @@ struct x265amd_encoder
         }
         if (me) x265amd_me_close(me);
         if (rateCtl) x265amd_rc_close(rateCtl);
+        if (dSaoPreCount) (void)hipFree(dSaoPreCount);
+        if (dSaoPreOrg) (void)hipFree(dSaoPreOrg);
         if (dSaoCount) (void)hipFree(dSaoCount);
         if (dSaoOrg) (void)hipFree(dSaoOrg);
         if (dSaoParams) (void)hipFree(dSaoParams);

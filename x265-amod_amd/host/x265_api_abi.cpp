@@ -19,6 +19,7 @@
 #include "../../include/x265amd_encoder.h"
 #include "x265_abi_layout.h"
 #include "x265_abi_layout_rskip.h"
+#include "x265_abi_layout_sao.h"
 #include "x265_abi_layout_ingest.h"
 #include "x265_api_table.h"
 #include <stdint.h>
@@ -204,7 +205,8 @@ int abi_param_parse(void* p, const char* name, const char* value)
         { "annexb", X265ABI_PARAM_bAnnexB }, { "repeat-headers", X265ABI_PARAM_bRepeatHeaders }, { "aud", X265ABI_PARAM_bEnableAccessUnitDelimiters }, { "hdr10", X265ABI_PARAM_bEmitHDR10SEI },
         { "hdr", X265ABI_PARAM_bEmitHDR10SEI }, { "cll", X265ABI_PARAM_bEmitCLL }, { "tskip", X265ABI_PARAM_bEnableTransformSkip }, { "lossless", X265ABI_PARAM_bLossless },
         { "hist-scenecut", X265ABI_PARAM_bHistBasedSceneCut },            /* (param.cpp:1279) */
-        { "psnr", X265ABI_PARAM_bEnablePsnr }, { "ssim", X265ABI_PARAM_bEnableSsim } };
+        { "psnr", X265ABI_PARAM_bEnablePsnr }, { "ssim", X265ABI_PARAM_bEnableSsim },
+        { "sao-non-deblock", X265ABI_PARAM_bSaoNonDeblocked }, { "limit-sao", X265ABI_PARAM_bLimitSAO } };            /* (param.cpp:1099, :1310) */
     if (!strcmp(key, "deblock") && !neg && value)
     {
         /* --deblock tc:beta | tc,beta | tc | a truth value (param.cpp:1083-1097) */
@@ -215,7 +217,13 @@ int abi_param_parse(void* p, const char* name, const char* value)
         { wr<int32_t>(p, X265ABI_PARAM_deblockingFilterTCOffset, tc); wr<int32_t>(p, X265ABI_PARAM_deblockingFilterBetaOffset, tc); wr<int32_t>(p, X265ABI_PARAM_bEnableLoopFilter, 1); return 0; }
     }
     for (const auto& sw : switches)
-        if (!strcmp(key, sw.name)) { const int v = truth(bad); if (bad) return -2; wr<int32_t>(p, sw.off, v); return 0; }
+        if (!strcmp(key, sw.name))
+        {
+            /* (a value that is no truth value is an error AND stores what x265_atobool made of it, param.cpp:57-68: 0 -- which a "no-" in front has turned round by then) */
+            const int v = truth(bad);
+            wr<int32_t>(p, sw.off, bad ? (neg ? 1 : 0) : v);
+            return bad ? -2 : 0;
+        }
     if (neg && !strcmp(key, "scenecut")) { wr<int32_t>(p, X265ABI_PARAM_scenecutThreshold, 0); return 0; }          /* --no-scenecut (param.cpp: atobool of "false") */
     if (neg) return -1;
     static const struct { const char* name; size_t off; } ints[] = {
@@ -226,7 +234,8 @@ int abi_param_parse(void* p, const char* name, const char* value)
         { "tu-inter-depth", X265ABI_PARAM_tuQTMaxInterDepth }, { "limit-tu", X265ABI_PARAM_limitTU }, { "rskip", X265ABI_PARAM_recursionSkipMode }, { "aq-mode", X265ABI_PARAM_rc_aqMode },
         { "qg-size", X265ABI_PARAM_rc_qgSize }, { "ctu", X265ABI_PARAM_maxCUSize }, { "min-cu-size", X265ABI_PARAM_minCUSize }, { "max-tu-size", X265ABI_PARAM_maxTUSize },
         { "slices", X265ABI_PARAM_maxSlices }, { "level-idc", X265ABI_PARAM_levelIdc }, { "log-level", X265ABI_PARAM_logLevel }, { "qpmin", X265ABI_PARAM_rc_qpMin }, { "qpmax", X265ABI_PARAM_rc_qpMax },
-        { "qpstep", X265ABI_PARAM_rc_qpStep }, { "csv-log-level", X265ABI_PARAM_csvLogLevel }, { "vbv-bufsize", X265ABI_PARAM_rc_vbvBufferSize }, { "vbv-maxrate", X265ABI_PARAM_rc_vbvMaxBitrate } };
+        { "qpstep", X265ABI_PARAM_rc_qpStep }, { "csv-log-level", X265ABI_PARAM_csvLogLevel }, { "vbv-bufsize", X265ABI_PARAM_rc_vbvBufferSize }, { "vbv-maxrate", X265ABI_PARAM_rc_vbvMaxBitrate },
+        { "selective-sao", X265ABI_PARAM_selectiveSAO } };            /* (param.cpp:1392-1395) */
     for (const auto& it : ints)
         if (!strcmp(key, it.name)) { const int v = num(bad); wr<int32_t>(p, it.off, v); return bad ? -2 : 0; }          /* (the reference stores what atoi made of a bad value, too) */
     static const struct { const char* name; size_t off; } reals[] = {
@@ -391,7 +400,6 @@ void* abi_encoder_open(void* p)
     REQUIRE(!PI(p, bIntraRefresh) && !PI(p, bEnableHME) && !PI(p, bEnableConstrainedIntra), "intra refresh / HME / constrained intra are not built");
     REQUIRE(!PI(p, noiseReductionIntra) && !PI(p, noiseReductionInter) && !rd<const char*>(p, X265ABI_PARAM_scalingLists), "noise reduction / scaling lists are not built");
     REQUIRE(!PI(p, cbQpOffset) && !PI(p, crQpOffset), "chroma QP offsets (cbQpOffset / crQpOffset) must be 0");
-    REQUIRE(!PI(p, bSaoNonDeblocked) && !PI(p, selectiveSAO), "sao-non-deblock / selective-sao are not built");
     REQUIRE(!PI(p, bEmitHRDSEI), "the HRD SEI (bEmitHRDSEI) is not built");
     REQUIRE(!PI(p, bEnableTemporalSubLayers) && !PI(p, uhdBluray) && !PI(p, bEnableSvtHevc), "temporal layers / uhd-bd / svt are not built");
     REQUIRE(!PI(p, analysisReuseMode) && !PI(p, bDynamicRefine) && !PI(p, rdPenalty) && !PI(p, bEnableRdRefine) && !PI(p, dynamicRd) && !PI(p, bSsimRd), "analysis reuse / rd-refine / dynamic-rd / ssim-rd are not built");
@@ -470,7 +478,12 @@ void* abi_encoder_open(void* p)
     const int ft = PI(p, frameNumThreads);
     const int ftAuto = q.bEnableWavefront ? 3 : ((ctuRows + 1) / 2 < 16 ? (ctuRows + 1) / 2 : 16);
     q.frameNumThreads = ft == 1 ? 1 : (ft > 16 ? 16 : (ft <= 0 ? ftAuto : ft));
-    x265amd_encoder* e = x265amd_encoder_open(&q);
+    /* --sao-non-deblock, --limit-sao, --selective-sao: Encoder::configure's rules for them are x265amd_encoder_open_ext's */
+    x265amd_param_ext ext;
+    memset(&ext, 0, sizeof(ext));
+    ext.size = sizeof(ext);
+    ext.bSaoNonDeblocked = PI(p, bSaoNonDeblocked) != 0; ext.bLimitSAO = PI(p, bLimitSAO) != 0; ext.selectiveSAO = PI(p, selectiveSAO);
+    x265amd_encoder* e = x265amd_encoder_open_ext(&q, &ext);
     if (!e) return nullptr;
     AbiEncoder* a = new AbiEncoder;
     a->enc = e; a->width = q.sourceWidth; a->height = q.sourceHeight;

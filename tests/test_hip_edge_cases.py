@@ -1,6 +1,7 @@
 """GPU edge cases of the drop-in boundary: empty batches, the installed primitive table (x265amd_setup_primitives), extreme
-QPs / all-zero and saturated residuals in the TU chain, neighbour-less and fully available intra blocks, PUs on the picture
-border with search windows reaching into the padding."""
+QPs / all-zero and saturated residuals in the TU chain, PUs on the picture border with search windows reaching into the
+padding.  (Neighbour-less and fully available intra blocks are not here: hevc_testlib.intra_cases draws them -- flags all 0 and
+all 1 -- for test_intra_golden and test_queue_ops.test_intra_scan.)"""
 import ctypes as C
 
 import numpy as np

@@ -25,6 +25,7 @@
 #include "inter_common.h"
 #include "xa_queue.h"
 #include "../host/cabac_coder.h"
+#include "rd_host.h"
 #include "inter_chain_dev.h"
 #include "inter_search_dev.h"
 #include <string.h>
@@ -61,20 +62,8 @@ void xa_timing_report()
 
 namespace {
 
-#if X265AMD_DEPTH < 10
-typedef uint32_t sse_t;
-#else
-typedef uint64_t sse_t;
-#endif
-
 enum { PRED_MERGE, PRED_SKIP, PRED_2Nx2N, PRED_BIDIR, PRED_INTRA, PRED_INTRA_NxN, PRED_2NxN, PRED_Nx2N, PRED_2NxnU, PRED_2NxnD, PRED_nLx2N, PRED_nRx2N, PRED_SPLIT, NUM_PRED };
 struct SplitData { uint32_t splitRefs, mvCost[2]; uint64_t sa8dCost; };
-const uint64_t kMaxCost = 0x7FFFFFFFFFFFFFFFULL;
-const uint8_t kChromaScale[58] = { 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23, 24, 25, 26, 27, 28, 29, 29, 30, 31,
-                                  32, 33, 33, 34, 34, 35, 35, 36, 36, 37, 37, 38, 39, 40, 41, 42, 43, 44, 45, 46, 47, 48, 49, 50, 51 };       /* g_chromaScale (4:2:0): the chroma QP of a luma QP */
-
-struct Snap { uint8_t ctx[X265AMD_CTX_STRIDE]; uint64_t frac; };
-
 struct Mode
 {
     x265amd_cu_unit u[256];         /* the CU's units, raster with row length size/4 */
@@ -102,14 +91,7 @@ struct Mode
 
 struct ModeDepth { Mode pred[NUM_PRED]; Mode* best; Snap cur; uint32_t mvCost2Nx2N[2]; x265amd_me_detail det; uint32_t srcMean, srcHomo; };
 
-struct DevBuf
-{
-    void* p = nullptr;
-    ~DevBuf() { xa_scratch_free(p); }
-    hipError_t alloc(size_t bytes) { return xa_scratch_alloc(&p, bytes ? bytes : 16); }
-};
-
-struct Analyzer
+struct Analyzer : RdCost
 {
     x265amd_me_ctx* me; hipStream_t st;
     const x265amd_mvpred_info* I; const x265amd_inter_search_params* S; const x265amd_slice_info* si; const x265amd_analysis_params* A;
@@ -121,7 +103,6 @@ struct Analyzer
     DevBuf dTiles, dPlanes;
     XaMapped dJobs;                         /* motion compensation jobs: host memory the kernel reads in place */
     size_t tileBytes;
-    uint64_t lambda2, lambda; uint32_t psyRd;
     x265amd_rd_params rp;
     int err;
     /* ---- delta QP (pps.bUseDQP): `qp` above is the QP in force -- what Search::setLambdaFromQP was last called with (search.cpp:177-187): the lambdas, the quantiser and the
@@ -138,9 +119,7 @@ struct Analyzer
         qp = q > 51 ? 51 : q;
         /* (the device-run inter chains carry one QP: none of them is on under delta QP, and without it no QP passes 51 -- the slice QP is clipped) */
         if (lambdaQp != qp && chain.on) return fail("a QP above 51 on a device-run chain");
-        uint64_t rd[6];
-        x265amd_rdcost(lambdaQp, si->slice_type, A->psy_rd, 0, 0, 0, rd);
-        lambda2 = rd[0]; lambda = rd[1]; psyRd = (uint32_t)rd[2];
+        setQP(lambdaQp, si->slice_type, A->psy_rd);
         return 0;
     }
     void cuQp2(x265amd_rd_cu& c) const { c.qp = (int8_t)qp; c.reserved[0] = (uint8_t)(lambdaQp != qp ? lambdaQp : 0); c.reserved[1] = (uint8_t)(maxTUDepth + 1); }
@@ -348,13 +327,7 @@ struct Analyzer
         J.tiles_per_depth = 2 * NUM_PRED + 6; J.cand_tile0 = 2 * NUM_PRED; J.split_recon_tile = NUM_PRED + PRED_SPLIT;
         J.skip_recon_tile = NUM_PRED + PRED_SKIP; J.merge_recon_tile = NUM_PRED + PRED_MERGE;
         J.frame_parallel = S->frame_parallel; J.search_range = S->search_range; J.chroma_sa8d = A->rd_level >= 3; J.slice_type = si->slice_type;
-        {
-            /* Quant::setQPforQuant (quant.cpp:221-244), chroma QP offsets 0: as make_plan (inter_rd.hip) */
-            const int qpQuant = qp < 0 ? 0 : (qp > 51 ? 51 : qp), bd = 6 * (X265AMD_DEPTH - 8);
-            int qpC = qpQuant < -bd ? -bd : (qpQuant > 57 ? 57 : qpQuant);
-            if (qpC >= 30) qpC = kChromaScale[qpC];
-            J.qp_luma = qpQuant + bd; J.qp_chroma = qpC + bd;
-        }
+        quantQps(qp, J.qp_luma, J.qp_chroma);
         J.tu_log2_max = si->tu_log2_max;
         J.ctu_x = ctuX; J.ctu_y = ctuY; J.lambda = lambda; J.lambda2 = lambda2; J.psy_rd = psyRd;
         J.dbg = 0;          /* (bits that leave single stores of the chain out: for timing them, never for a stream) */
@@ -624,11 +597,8 @@ struct Analyzer
     int reconTile(int depth, int k) const { return depth * (2 * NUM_PRED + 6) + NUM_PRED + k; }
     int candTile(int depth, int k) const { return depth * (2 * NUM_PRED + 6) + 2 * NUM_PRED + k; }
 
-    uint64_t calcRdCost(sse_t d, uint32_t b) const { return d + (((uint64_t)b * lambda2 + 128) >> 8); }
-    uint64_t calcPsyRdCost(sse_t d, uint32_t b, uint32_t e) const { return d + ((lambda * psyRd * e) >> 24) + (((uint64_t)b * lambda2) >> 8); }
-    uint64_t calcRdSADCost(uint32_t d, uint32_t b) const { return d + (((uint64_t)b * lambda + 128) >> 8); }
     uint32_t getCost(uint32_t b) const { return (uint32_t)(((uint64_t)b * lambda + 128) >> 8); }
-    void updateModeCost(Mode& m) const { m.rdCost = psyRd ? calcPsyRdCost(m.distortion, m.totalBits, m.psyEnergy) : calcRdCost(m.distortion, m.totalBits); }
+    void updateModeCost(Mode& m) const { m.rdCost = cost(m.distortion, m.totalBits, m.psyEnergy); }
 
     /* m_bChromaSa8d (analysis.cpp:707): SA8D ranking includes chroma from rd level 3 */
     uint32_t sa8dOf(const x265amd_cu_measure& ms) const { return A->rd_level >= 3 ? ms.sa8d : ms.sa8d_luma; }
@@ -1095,12 +1065,7 @@ struct Analyzer
         J.planes = (uint64_t)(uintptr_t)dPlanes.p; J.luma_tab = (uint64_t)(uintptr_t)chain.mLuma.p;
         J.pred_tile = tileAddr(predTile(depth, PRED_2Nx2N)); J.recon_tile = tileAddr(reconTile(depth, PRED_2Nx2N));
         J.lambda = lambda; J.lambda2 = lambda2; J.psy_rd = psyRd;
-        {
-            const int qpQuant = qp < 0 ? 0 : (qp > 51 ? 51 : qp), bd = 6 * (X265AMD_DEPTH - 8);
-            int qpC = qpQuant < -bd ? -bd : (qpQuant > 57 ? 57 : qpQuant);
-            if (qpC >= 30) qpC = kChromaScale[qpC];
-            J.qp_luma = qpQuant + bd; J.qp_chroma = qpC + bd;
-        }
+        quantQps(qp, J.qp_luma, J.qp_chroma);
         J.sign_hide = si->sign_hide != 0; J.chroma_sa8d = A->rd_level >= 3; J.rd_level = A->rd_level; J.do_rd = 1; J.slice_type = si->slice_type;
         {
             const x265amd_cu_unit* l = (x >> 2) > 0 ? &units[(y >> 2) * w4 + (x >> 2) - 1] : nullptr;

@@ -19,6 +19,7 @@
 #include "x265amd_dev.h"
 #include "x265amd_host.h"
 #include "../host/cabac_coder.h"
+#include "rd_host.h"
 #include <string.h>
 #include <vector>
 #include <functional>
@@ -47,15 +48,6 @@ static bool measure_use_wg(int n) { return n <= 64; }
 /* ---------------- host: the reference's walk ---------------- */
 namespace {
 
-#if X265AMD_DEPTH < 10
-typedef uint32_t sse_t;             /* common/common.h:142-146 */
-#else
-typedef uint64_t sse_t;
-#endif
-
-struct Snap { uint8_t ctx[X265AMD_CTX_STRIDE]; uint64_t frac; };
-struct Cost { uint64_t rdcost; uint32_t bits; sse_t distortion; uint32_t energy; };       /* search.h:  struct Cost */
-const uint64_t kMaxCost = 0x7FFFFFFFFFFFFFFFULL;
 const uint32_t kCtxCbf[3][5] = { { 1, 0, 0, 0, 0 }, { 2, 3, 4, 5, 6 }, { 2, 3, 4, 5, 6 } };          /* contexts.h:120 */
 
 struct CuPlan
@@ -66,24 +58,17 @@ struct CuPlan
     int chromaRes[5][3];            /* the same of chroma layer C and plane 1 / 2 */
 };
 
-inline uint32_t zorder_in_cu(int x4, int y4)
-{
-    uint32_t z = 0;
-    for (int b = 0; b < 4; b++) z |= (((uint32_t)x4 >> b) & 1) << (2 * b) | (((uint32_t)y4 >> b) & 1) << (2 * b + 1);
-    return z;
-}
 inline size_t host_layer_offset(int plane, int layer)
 {
     return plane ? (size_t)4 * RD_LUMA_ELEMS + (size_t)((layer - 2) * 2 + (plane - 1)) * RD_CHROMA_ELEMS : (size_t)(layer - 2) * RD_LUMA_ELEMS;
 }
 
-struct Walker
+struct Walker : RdCost
 {
     x265amd_cabac& c;
     const CuPlan& P;
     const x265amd_tu_result* res;   /* all results of the launch */
     const int16_t* levels;          /* this CU's level scratch (host copy), RD_SCRATCH_ELEMS */
-    uint64_t lambda2, lambda; uint32_t psyRd;
     Snap rqtRoot[6], rqtTest[6];
 
     /* RDOQ: the transform units are not quantised ahead of the walk; `demand(first job, count, luma?, size, tuDepth)` runs them when the walk reaches them,
@@ -114,18 +99,12 @@ struct Walker
         return (plane ? P.chromaRes[layer][plane] : P.lumaRes[layer]) + ty * nt + tx;
     }
 
-    /* Entropy: getNumberOfWrittenBits / resetBits / load / store / bitsCodeBin (entropy.h:120-140, :219-224; entropy.cpp:2445-2455) */
+    /* Entropy: getNumberOfWrittenBits / resetBits / bitsCodeBin (entropy.h:120-140, :219-224; entropy.cpp:2445-2455) */
     uint32_t bits() const { return (uint32_t)(c.fracBits >> 15); }
     void resetBits() { c.fracBits &= 32767; }
-    void store(Snap& s) const { memcpy(s.ctx, c.ctx, X265AMD_CTX_STRIDE); s.frac = c.fracBits; }
-    void load(const Snap& s) { memcpy(c.ctx, s.ctx, X265AMD_CTX_STRIDE); c.fracBits = s.frac; }
     uint32_t bitsCodeBin(uint32_t bin, int ctxIdx) const { return (uint32_t)(((c.fracBits & 32767) + k_bits[c.ctx[ctxIdx] ^ bin]) >> 15); }
     uint32_t estimateCbfBits(uint32_t cbf, int ttype, int tuDepth) const { return bitsCodeBin(cbf, C_QT_CBF + (int)kCtxCbf[ttype][tuDepth]); }
 
-    /* RDCost (rdcost.h:99-153) */
-    uint64_t calcRdCost(sse_t dist, uint32_t b) const { return dist + (((uint64_t)b * lambda2 + 128) >> 8); }
-    uint64_t calcPsyRdCost(sse_t dist, uint32_t b, uint32_t energy) const { return dist + ((lambda * psyRd * energy) >> 24) + (((uint64_t)b * lambda2) >> 8); }
-    uint64_t cost(sse_t dist, uint32_t b, uint32_t energy) const { return psyRd ? calcPsyRdCost(dist, b, energy) : calcRdCost(dist, b); }
     uint64_t estimateNullCbfCost(sse_t dist, uint32_t energy, int tuDepth, int ttype) const { return cost(dist, estimateCbfBits(0, ttype, tuDepth), energy); }
 
     x265amd_cu_unit& U(int x, int y) { return c.U(x >> 2, y >> 2); }
@@ -176,7 +155,7 @@ struct Walker
         uint32_t cbfFlag[3] = { 0, 0, 0 }, singleBits[3] = { 0, 0, 0 }, singleEnergy[3] = { 0, 0, 0 };
         sse_t singleDist[3] = { 0, 0, 0 };
 
-        store(rqtRoot[depth]);
+        store(rqtRoot[depth], c);
 
         uint8_t nodeStartCtx[X265AMD_CTX_STRIDE];
         bool chromaAhead = false;
@@ -258,7 +237,7 @@ struct Walker
                 }
 
             /* the flags are priced from the node's start state; the coefficient bits were collected above (:3652-3690) */
-            load(rqtRoot[depth]);
+            load(c, rqtRoot[depth]);
             resetBits();
             if (codeChroma)
             {
@@ -293,8 +272,8 @@ struct Walker
         {
             if (bCheckFull)
             {
-                store(rqtTest[depth]);
-                load(rqtRoot[depth]);
+                store(rqtTest[depth], c);
+                load(c, rqtRoot[depth]);
             }
             Cost splitCost = { 0, 0, 0, 0 };
             if (bSplitPresentFlag && (log2TrSize <= P.range[1] && log2TrSize > P.range[0]))
@@ -317,7 +296,7 @@ struct Walker
                 else
                     outCosts.energy += splitCost.energy;
             }
-            load(rqtTest[depth]);
+            load(c, rqtTest[depth]);
             /* RDOQ: an 8x8 node and its 4x4 children own the SAME 4x4 chroma blocks (one slot in the scratch, where the reference has one buffer per
              * layer); the children's pass re-quantised them under its own entropy state.  The full node won: bring its version back */
             if (demand && !err && bCheckFull && codeChroma && log2TrSize == 3)
@@ -362,7 +341,7 @@ struct Walker
         U(x, y).cbf[1] |= (uint8_t)(ucbf << tuDepth);
         U(x, y).cbf[2] |= (uint8_t)(vcbf << tuDepth);
 
-        load(rqtRoot[depth]);
+        load(c, rqtRoot[depth]);
         resetBits();
         codeInterSubdivCbfQT(x, y, tuDepth);
         splitCost.bits += bits();
@@ -407,7 +386,7 @@ struct Walker
         }
         const int trSize = 1 << log2TrSize;
         const int ux = (x - P.x) >> 2, uy = (y - P.y) >> 2;
-        const uint32_t z = zorder_in_cu(ux, uy);
+        const uint32_t z = zUnit(ux, uy);
         if (cbfBit(x, y, 0, tuDepth))
             for (int yy = 0; yy < trSize >> 2; yy++) for (int xx = 0; xx < trSize >> 2; xx++) sel[(uy + yy) * 16 + ux + xx] = (uint8_t)log2TrSize;
         if (coeffCu) memcpy(coeffCu + (z << 4), nodeLevels(0, log2TrSize, x, y), sizeof(int16_t) << (2 * log2TrSize));
@@ -425,32 +404,13 @@ struct Walker
     }
 };
 
-struct DevBuf
-{
-    void* p = nullptr;
-    ~DevBuf() { xa_scratch_free(p); }
-    hipError_t alloc(size_t bytes) { return xa_scratch_alloc(&p, bytes ? bytes : 16); }
-};
-
 } // namespace
-
-/* the QP of a CU's lambdas (x265amd_rd_cu.reserved[0] when it differs from the quantiser's: QPs above 51) */
-static inline int lambda_qp(const x265amd_rd_cu& cu) { return cu.reserved[0] ? (int)cu.reserved[0] : (int)cu.qp; }
-/* RDCost::setQP for one CU */
-static void rd_lambdas(const x265amd_slice_info* si, const x265amd_rd_params* rp, int qp, Walker& w)
-{
-    uint64_t rd[6];
-    x265amd_rdcost(qp, si->slice_type, rp->psy_rd, 0, 0, 0, rd);
-    w.lambda2 = rd[0]; w.lambda = rd[1]; w.psyRd = (uint32_t)rd[2];
-}
 
 /* the nodes of one CU's tree; jobs == NULL: only the plan */
 static int make_plan(const x265amd_slice_info* si, const x265amd_rd_cu& cu, int part, CuPlan& P, int firstJob, const uint64_t* src, intptr_t stride, intptr_t cstride,
                      uint64_t tile, uint64_t scratch, std::vector<x265amd_tu_job>* jobs, uint64_t levels = 0)
 {
     XA_HOSTPROF("rd.make_plan");
-    static const uint8_t chromaScale[58] = { 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23, 24, 25, 26, 27, 28, 29, 29, 30, 31,
-                                             32, 33, 33, 34, 34, 35, 35, 36, 36, 37, 37, 38, 39, 40, 41, 42, 43, 44, 45, 46, 47, 48, 49, 50, 51 };       /* H.265 table 8-10 */
     P.x = cu.x; P.y = cu.y; P.log2 = cu.log2_size; P.size = 1 << P.log2; P.depth = 6 - P.log2; P.qp = cu.qp;
     if (P.log2 < 3 || P.log2 > 6 || (P.x & (P.size - 1)) || (P.y & (P.size - 1)) || P.x < 0 || P.y < 0 || P.x + P.size > si->pic_width || P.y + P.size > si->pic_height)
         return xa_fail(X265AMD_EINVAL, "inter_residual_rd: CU outside the picture or misaligned");
@@ -461,11 +421,8 @@ static int make_plan(const x265amd_slice_info* si, const x265amd_rd_cu& cu, int 
     P.range[0] = lo < (uint32_t)si->tu_log2_min ? si->tu_log2_min : (lo > (uint32_t)si->tu_log2_max ? si->tu_log2_max : (int)lo);
     P.range[1] = si->tu_log2_max;
     if (P.range[0] < 2 || P.range[1] > 5 || P.range[0] > P.range[1]) return xa_fail(X265AMD_EINVAL, "inter_residual_rd: transform size range");
-    /* Quant::setQPforQuant (quant.cpp:221-244), chroma QP offsets 0 */
-    const int qpQuant = P.qp < 0 ? 0 : (P.qp > 51 ? 51 : P.qp);
-    const int bd = 6 * (X265AMD_DEPTH - 8);
-    int qpC = qpQuant < -bd ? -bd : (qpQuant > 57 ? 57 : qpQuant);
-    if (qpC >= 30) qpC = chromaScale[qpC];
+    int qpLumaScaled, qpChromaScaled;
+    quantQps(P.qp, qpLumaScaled, qpChromaScaled);
     const int hi = P.log2 < P.range[1] ? P.log2 : P.range[1];
     for (int L = 0; L < 6; L++) P.lumaRes[L] = -1;
     for (int C = 0; C < 5; C++) P.chromaRes[C][0] = P.chromaRes[C][1] = P.chromaRes[C][2] = -1;
@@ -482,7 +439,7 @@ static int make_plan(const x265amd_slice_info* si, const x265amd_rd_cu& cu, int 
         P.lumaRes[L] = count;
         count += nt * nt;
         if (!jobs) continue;
-        j.log2_tr_size = (uint8_t)L; j.ttype = 0; j.qp_scaled = (uint8_t)(qpQuant + bd);
+        j.log2_tr_size = (uint8_t)L; j.ttype = 0; j.qp_scaled = (uint8_t)qpLumaScaled;
         j.fenc_stride = (int32_t)stride; j.pred_stride = 64; j.resi_stride = 64; j.recon_stride = 64;
         for (int ty = 0; ty < nt; ty++)
             for (int tx = 0; tx < nt; tx++)
@@ -506,7 +463,7 @@ static int make_plan(const x265amd_slice_info* si, const x265amd_rd_cu& cu, int 
             P.chromaRes[C][p] = count;
             count += nt * nt;
             if (!jobs) continue;
-            j.log2_tr_size = (uint8_t)C; j.ttype = (uint8_t)p; j.qp_scaled = (uint8_t)(qpC + bd);
+            j.log2_tr_size = (uint8_t)C; j.ttype = (uint8_t)p; j.qp_scaled = (uint8_t)qpChromaScaled;
             j.fenc_stride = (int32_t)cstride; j.pred_stride = 32; j.resi_stride = 32; j.recon_stride = 32;
             for (int ty = 0; ty < nt; ty++)
                 for (int tx = 0; tx < nt; tx++)
@@ -605,7 +562,7 @@ static int inter_rd_walk_impl(const x265amd_slice_info* si, const x265amd_rd_par
             memcpy(&units[((P.y >> 2) + yy) * w4 + (P.x >> 2)], &mine[yy * u4], sizeof(x265amd_cu_unit) * u4);
         }
         Walker w(*coder, P, res, (const int16_t*)((const char*)levels + levels_stride_bytes * i));
-        rd_lambdas(si, rp, lambda_qp(cu), w);
+        w.setQP(lambdaQpOf(cu), si->slice_type, rp->psy_rd);
         for (int yy = 0; yy < u4; yy++)
             for (int xx = 0; xx < u4; xx++)
             {
@@ -617,7 +574,7 @@ static int inter_rd_walk_impl(const x265amd_slice_info* si, const x265amd_rd_par
         memcpy(cur.ctx, cu.ctx, X265AMD_CTX_COUNT);
         cur.frac = cu.frac_bits;
 
-        w.load(cur);
+        load(*coder, cur);
         Cost costs = { 0, 0, 0, 0 };
         w.limitTU = rp->limit_tu;
         if (rp->limit_tu >= 3)
@@ -644,7 +601,7 @@ static int inter_rd_walk_impl(const x265amd_slice_info* si, const x265amd_rd_par
         sse_t cbf0Dist = (sse_t)m0.sse[0];
         cbf0Dist += (sse_t)m0.sse[1];
         cbf0Dist += (sse_t)m0.sse[2];
-        w.load(cur);
+        load(*coder, cur);
         w.resetBits();
         coder->bin(0, C_QT_ROOT_CBF);
         const uint32_t cbf0Bits = w.bits();
@@ -662,7 +619,7 @@ static int inter_rd_walk_impl(const x265amd_slice_info* si, const x265amd_rd_par
         if (rootCbf) w.collect(P.x, P.y, 0, sel + (size_t)RD_SEL_BYTES * i, coeffCu.data());
 
         /* signal bits of the inter / merge / skip coded CU (:2900-2930) */
-        w.load(cur);
+        load(*coder, cur);
         w.resetBits();
         uint32_t coeffBits, bits, mvBits;
         const x265amd_cu_unit* l = coder->at((P.x >> 2) - 1, P.y >> 2);
@@ -744,14 +701,14 @@ extern "C" void x265amd_inter_rd_finish(const x265amd_slice_info* si, const x265
         const x265amd_cu_measure& m1 = final_meas[i];
         x265amd_rd_result& r = out[i];
         uint64_t rd[6];
-        x265amd_rdcost(lambda_qp(cus[i]), si->slice_type, rp->psy_rd, 0, 0, 0, rd);
+        x265amd_rdcost(lambdaQpOf(cus[i]), si->slice_type, rp->psy_rd, 0, 0, 0, rd);
         const sse_t bestLumaDist = (sse_t)m1.sse[0];
         sse_t bestChromaDist = (sse_t)m1.sse[1];
         bestChromaDist += (sse_t)m1.sse[2];
         const sse_t distortion = bestLumaDist + bestChromaDist;
         r.luma_distortion = (uint32_t)bestLumaDist; r.chroma_distortion = (uint32_t)bestChromaDist; r.distortion = distortion;
         r.psy_energy = rd[2] ? m1.psy : 0;
-        x265amd_rdcost(lambda_qp(cus[i]), si->slice_type, rp->psy_rd, distortion, r.total_bits, r.psy_energy, rd);
+        x265amd_rdcost(lambdaQpOf(cus[i]), si->slice_type, rp->psy_rd, distortion, r.total_bits, r.psy_energy, rd);
         r.rd_cost = rd[2] ? rd[4] : rd[3];
     }
 }
@@ -808,10 +765,10 @@ extern "C" int x265amd_skip_rd_host(const x265amd_slice_info* si, const x265amd_
         chroma += (sse_t)m.sse[2];
         const sse_t distortion = luma + chroma;
         uint64_t rd[6];
-        x265amd_rdcost(lambda_qp(cu), si->slice_type, rp->psy_rd, 0, 0, 0, rd);
+        x265amd_rdcost(lambdaQpOf(cu), si->slice_type, rp->psy_rd, 0, 0, 0, rd);
         r.luma_distortion = (uint32_t)luma; r.chroma_distortion = (uint32_t)chroma; r.distortion = distortion; r.res_energy = (uint32_t)luma;
         r.psy_energy = rd[2] ? m.psy : 0;
-        x265amd_rdcost(lambda_qp(cu), si->slice_type, rp->psy_rd, distortion, r.total_bits, r.psy_energy, rd);
+        x265amd_rdcost(lambdaQpOf(cu), si->slice_type, rp->psy_rd, distortion, r.total_bits, r.psy_energy, rd);
         r.rd_cost = rd[2] ? rd[4] : rd[3];
         memcpy(r.ctx, coder->ctx, X265AMD_CTX_COUNT);
         r.frac_bits = coder->fracBits;

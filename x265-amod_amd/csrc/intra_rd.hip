@@ -14,37 +14,13 @@
 #include "x265amd_host.h"
 #include "xa_queue.h"
 #include "../host/cabac_coder.h"
+#include "rd_host.h"
 #include <string.h>
 #include <atomic>
 #include <mutex>
 #include <vector>
 
 namespace {
-
-#if X265AMD_DEPTH < 10
-typedef uint32_t sse_t;
-#else
-typedef uint64_t sse_t;
-#endif
-
-struct Snap { uint8_t ctx[X265AMD_CTX_STRIDE]; uint64_t frac; };
-struct Cost { uint64_t rdcost; uint32_t bits; sse_t distortion; uint32_t energy; };
-const uint64_t kMaxCost = 0x7FFFFFFFFFFFFFFFULL;
-
-struct DevBuf
-{
-    void* p = nullptr;
-    ~DevBuf() { xa_scratch_free(p); }
-    hipError_t alloc(size_t bytes) { return xa_scratch_alloc(&p, bytes ? bytes : 16); }
-};
-struct MappedBuf : XaMapped { void free() { xa_mapped_free(p); p = nullptr; } };
-
-inline unsigned zUnit(int ux, int uy)           /* z-order of unit (ux, uy) inside its CTU */
-{
-    unsigned r = 0;
-    for (int b = 0; b < 4; b++) r |= (((unsigned)ux >> b) & 1u) << (2 * b) | (((unsigned)uy >> b) & 1u) << (2 * b + 1);
-    return r;
-}
 
 /* The device-side records of a chain of 8x8 CUs (four x265amd_intra_peer + one x265amd_intra_chain) come from a list of their own, not from the pools: the counts in them
  * only ever grow (one counter for the process), so whatever a workgroup still holds of such a record from an earlier chain is an OLDER count and at worst makes it look
@@ -71,7 +47,42 @@ static void chain_block_put(void* p)
     g_chainFree.push_back(p);
 }
 
-struct IntraRd
+/* what every CU entry point is given: the picture, the CU and the tiles of the mode tried */
+struct IntraCall
+{
+    void* stream; const x265amd_slice_info* si; const x265amd_rd_params* rp; x265amd_cu_unit* units; const uint64_t* h_src; const uint64_t* h_rec;
+    intptr_t stride, cstride; const x265amd_rd_cu* cu; uint64_t d_pred, d_recon;
+    /* the refusals before anything is touched; missingOut: the entry returns a result and has nowhere to put it */
+    int refuse(bool missingOut, int partSize) const
+    {
+        if (!si || !rp || !units || !h_src || !h_rec || !cu || missingOut || !d_pred || !d_recon) return xa_fail(X265AMD_EINVAL, "intra rd: null argument");
+        if (si->tq_bypass_enabled) return xa_fail(X265AMD_EINVAL, "intra rd: lossless coding is not supported");
+        if (partSize != 0 && (partSize != 3 || cu->log2_size != 3 || si->tu_log2_min > 2)) return xa_fail(X265AMD_EINVAL, "intra rd: NxN only for 8x8 CUs with 4x4 transforms");
+        return X265AMD_OK;
+    }
+};
+
+/* The bit-counting coder of one call and the CU's units as the caller had them: the units go back and the coder is closed on every way out. */
+struct CuScope
+{
+    x265amd_cabac* coder = nullptr;
+    x265amd_cu_unit* first = nullptr; int w4 = 0, u4 = 0;          /* the CU's first unit in the picture's map, the map's row length, the CU's extent in units */
+    std::vector<x265amd_cu_unit> saved;
+    x265amd_cu_unit* row(int yy) const { return first + (size_t)yy * w4; }
+    void save(x265amd_cu_unit* first_, int w4_, int u4_)
+    {
+        first = first_; w4 = w4_; u4 = u4_;
+        saved.resize((size_t)u4 * u4);
+        for (int yy = 0; yy < u4; yy++) memcpy(&saved[(size_t)yy * u4], row(yy), sizeof(x265amd_cu_unit) * u4);
+    }
+    ~CuScope()
+    {
+        for (int yy = 0; yy < u4; yy++) memcpy(row(yy), &saved[(size_t)yy * u4], sizeof(x265amd_cu_unit) * u4);
+        if (coder) x265amd_cabac_close(coder);
+    }
+};
+
+struct IntraRd : RdCost
 {
     hipStream_t st;
     const x265amd_slice_info* si; const x265amd_rd_params* rp;
@@ -81,7 +92,6 @@ struct IntraRd
     int range[2];
     x265amd_cabac* c;
     Snap cur, rqtRoot[6], rqtTest[6];
-    uint64_t lambda2, lambda; uint32_t psyRd;
     uint64_t predTile, reconTile;
     DevBuf dResi, dLayer, dCand;
     MappedBuf dJobs; XaMapped dScanJob, dPuJob, dNxnJob; XaMappedOut dRes, dCoeff, dScan, dPuOut, dNxnOut;
@@ -104,7 +114,17 @@ struct IntraRd
     ~IntraRd();
     /* A 16x16 CU's 2Nx2N evaluation started BEFORE the recursion into its four 8x8 CUs, on a third queue, and collected after it (xa_check_intra_begin_ws):
      * it reads only what lies outside the CU and writes only its own tiles (no_picture), so it runs beside the sub-CUs, which own the picture meanwhile. */
-    struct Big { void* q = nullptr; bool on = false, owned = false; int x = 0, y = 0; DevBuf cand, coeffDev; XaMapped job; XaMappedOut out, levels, clevels; } big[2];    /* [0] 16x16 (third queue), [1] 32x32 (fourth) */
+    enum { MAX_JOBS = 16 };
+    struct Big
+    {
+        void* q = nullptr; bool on = false, owned = false; int x = 0, y = 0; DevBuf cand, coeffDev; XaMapped job; XaMappedOut out, levels, clevels;
+        bool alloc()
+        {
+            return cand.alloc((size_t)MAX_JOBS * 2048 * sizeof(pixel)) == hipSuccess && coeffDev.alloc((size_t)MAX_JOBS * 1024 * 2 * 2) == hipSuccess &&
+                   job.alloc(sizeof(x265amd_intra_nxn_job)) == hipSuccess && out.alloc(sizeof(x265amd_intra_nxn_out)) == hipSuccess &&
+                   levels.alloc(1024 * 2) == hipSuccess && clevels.alloc(2 * 256 * 2) == hipSuccess;
+        }
+    } big[2];          /* [0] 16x16 (third queue), [1] 32x32 (fourth) */
     const int16_t* curLevels = nullptr; const int16_t* curCLevels = nullptr;       /* where the last device-decided large unit left its levels */
     /* The intra try of a CU of a P / B picture (checkIntraInInter + encodeIntraInInter) as ONE command with the mode picked on the device (pick_sa8d), started at
      * the CU's entry on the queue of its depth (second, third, fourth: 32x32, 16x16, 8x8) and collected when the analysis gets to it -- after the recursion into
@@ -112,7 +132,6 @@ struct IntraRd
     Big inter[3];      /* job / result / level records: host memory the kernels read and write in place (x265amd_host.h) */
     XaMapped mCtx, mEstJob, mRdoq;                      /* RDOQ: the contexts the bit-estimate table is made from, its job record, the per-job RDOQ records */
     DevBuf dEst;                                        /* Entropy::m_estBitsSbac */
-    enum { MAX_JOBS = 16 };
     /* a luma TU whose chain already ran in a batch (the candidates of one partition share their neighbours, so they run as one launch):
      * codeIntraLumaQT takes the result instead of launching; the winner's prediction / reconstruction are copied when it is measured again */
     struct Pre { bool on; int x, y, log2; x265amd_tu_result r; const int16_t* lv; uint64_t recon, pred; bool copyBlocks; } pre;
@@ -120,17 +139,30 @@ struct IntraRd
     std::vector<int16_t> coeffC[2], coeffCBest[2];
     int err;
 
-    /* ---- entropy / cost helpers (as in inter_rd.hip) ---- */
+    /* ---- entropy / cost helpers (the shared ones: rd_host.h) ---- */
     uint32_t bits() const { return (uint32_t)(c->fracBits >> 15); }
     void resetBits() { c->fracBits &= 32767; }
-    void store(Snap& s) const { memcpy(s.ctx, c->ctx, X265AMD_CTX_STRIDE); s.frac = c->fracBits; }
-    void load(const Snap& s) { memcpy(c->ctx, s.ctx, X265AMD_CTX_STRIDE); c->fracBits = s.frac; }
-    uint64_t calcRdCost(sse_t d, uint32_t b) const { return d + (((uint64_t)b * lambda2 + 128) >> 8); }
-    uint64_t calcPsyRdCost(sse_t d, uint32_t b, uint32_t e) const { return d + ((lambda * psyRd * e) >> 24) + (((uint64_t)b * lambda2) >> 8); }
-    uint64_t cost(sse_t d, uint32_t b, uint32_t e) const { return psyRd ? calcPsyRdCost(d, b, e) : calcRdCost(d, b); }
-    uint64_t calcRdSADCost(uint32_t d, uint32_t b) const { return d + (((uint64_t)b * lambda + 128) >> 8); }
 
     x265amd_cu_unit& U(int x, int y) { return c->U(x >> 2, y >> 2); }
+    /* what a CU of a P / B slice codes first: the skip flag (not skipped) and the prediction mode (intra); returns the bits behind the skip flag */
+    uint32_t codeSkipAndPredMode()
+    {
+        if (si->slice_type == 2) return 0;
+        const x265amd_cu_unit* l = c->at((cuX >> 2) - 1, cuY >> 2);
+        const x265amd_cu_unit* a = c->at(cuX >> 2, (cuY >> 2) - 1);
+        c->bin(0, C_SKIP + (x265amd_cabac::coded(l) && l->pred_mode == X265AMD_MODE_SKIP) + (x265amd_cabac::coded(a) && a->pred_mode == X265AMD_MODE_SKIP));
+        const uint32_t skipFlagBits = bits();
+        c->bin(1, C_PRED_MODE);
+        return skipFlagBits;
+    }
+    /* bitsIntraModeNonMPM / bitsIntraModeMPM (entropy.h:196-197, :219-224) priced from the CU's start contexts: a mode outside the three predictors, the common part of one inside */
+    uint32_t nonMpmBits() const { return (uint32_t)(((cur.frac & 32767) + k_bits[cur.ctx[C_ADI] ^ 0]) >> 15) + 5; }
+    uint32_t mpmBaseBits() const { return (uint32_t)(((cur.frac & 32767) + k_bits[cur.ctx[C_ADI] ^ 1]) >> 15); }
+    uint32_t modeBits(const uint32_t preds[3], uint32_t mode) const
+    {
+        for (int i = 0; i < 3; i++) if (preds[i] == mode) return mpmBaseBits() + (mode == preds[0] ? 1u : 2u);
+        return nonMpmBits();
+    }
     bool cbfBit(int x, int y, int plane, int d) { return (U(x, y).cbf[plane] >> d) & 1; }
     void setTuDepth(int x, int y, int sz, int d) { for (int yy = y; yy < y + sz; yy += 4) for (int xx = x; xx < x + sz; xx += 4) U(xx, yy).tu_depth = (uint8_t)d; }
     void setCbf(int plane, int x, int y, int sz, int v) { for (int yy = y; yy < y + sz; yy += 4) for (int xx = x; xx < x + sz; xx += 4) U(xx, yy).cbf[plane] = (uint8_t)v; }
@@ -266,7 +298,7 @@ struct IntraRd
         const uint64_t layerRecon = (uint64_t)(uintptr_t)dLayer.p + ((size_t)layer * 4096 + (size_t)(y - cuY) * 64 + (x - cuX)) * isz;
         if (mightNotSplit)
         {
-            if (mightSplit) store(rqtRoot[fullDepth]);
+            if (mightSplit) store(rqtRoot[fullDepth], *c);
             x265amd_cu_unit& u = U(x, y);
             x265amd_tu_result r;
             int16_t* lv = coeffL[layer].data() + ((size_t)zInCu(x, y) << 4);
@@ -297,14 +329,7 @@ struct IntraRd
             const bool firstOfCu = x == cuX && y == cuY;
             if (firstOfCu)
             {
-                if (si->slice_type != 2)
-                {
-                    const x265amd_cu_unit* l = c->at((cuX >> 2) - 1, cuY >> 2);
-                    const x265amd_cu_unit* a = c->at(cuX >> 2, (cuY >> 2) - 1);
-                    const int skipCtx = (x265amd_cabac::coded(l) && l->pred_mode == X265AMD_MODE_SKIP) + (x265amd_cabac::coded(a) && a->pred_mode == X265AMD_MODE_SKIP);
-                    c->bin(0, C_SKIP + skipCtx);
-                    c->bin(1, C_PRED_MODE);
-                }
+                codeSkipAndPredMode();
                 c->partSize(u, depth, size);
             }
             if (U(cuX, cuY).part_size == 0)
@@ -333,8 +358,8 @@ struct IntraRd
         {
             if (mightNotSplit)
             {
-                store(rqtTest[fullDepth]);
-                load(rqtRoot[fullDepth]);
+                store(rqtTest[fullDepth], *c);
+                load(*c, rqtRoot[fullDepth]);
             }
             Cost splitCost = { 0, 0, 0, 0 };
             uint32_t cbf = 0;
@@ -358,7 +383,7 @@ struct IntraRd
                 outCost.rdcost += splitCost.rdcost; outCost.distortion += splitCost.distortion; outCost.bits += splitCost.bits; outCost.energy += splitCost.energy;
                 return 0;
             }
-            load(rqtTest[fullDepth]);
+            load(*c, rqtTest[fullDepth]);
             setTuDepth(x, y, trSize, tuDepth);
             setCbf(0, x, y, trSize, bCBF);
         }
@@ -416,14 +441,9 @@ struct IntraRd
         xa_phase(XA_PH_INTRA_SCAN);
         uint32_t preds[3];
         c->lumaPreds(x, y, preds);
-        const uint64_t frac = cur.frac & 32767;
-        const uint8_t adi = cur.ctx[C_ADI];
-        const uint32_t rbits = (uint32_t)((frac + k_bits[adi ^ 0]) >> 15) + 5;
-        const uint32_t mpmBase = (uint32_t)((frac + k_bits[adi ^ 1]) >> 15);
         for (uint32_t mode = 0; mode < 35; mode++)
         {
-            uint32_t b = rbits;
-            for (int i = 0; i < 3; i++) if (preds[i] == mode) { b = mpmBase + (mode == preds[0] ? 1u : 2u); break; }
+            const uint32_t b = modeBits(preds, mode);
             modeBitsOut[mode] = b; sadOut[mode] = (uint32_t)sa8d[mode];
             modeCosts[mode] = calcRdSADCost((uint32_t)sa8d[mode], b);
         }
@@ -467,18 +487,11 @@ struct IntraRd
             nj.num_units = (uint8_t)devUnits; nj.unit_log2 = (uint8_t)devLog2;
             {
                 /* what codeIntraLumaQT codes in front of the first unit's direction: skip flag and prediction mode (P / B slices), the partition size */
-                load(cur); resetBits();
-                if (si->slice_type != 2)
-                {
-                    const x265amd_cu_unit* l = c->at((cuX >> 2) - 1, cuY >> 2);
-                    const x265amd_cu_unit* a = c->at(cuX >> 2, (cuY >> 2) - 1);
-                    const int skipCtx = (x265amd_cabac::coded(l) && l->pred_mode == X265AMD_MODE_SKIP) + (x265amd_cabac::coded(a) && a->pred_mode == X265AMD_MODE_SKIP);
-                    c->bin(0, C_SKIP + skipCtx);
-                    c->bin(1, C_PRED_MODE);
-                }
+                load(*c, cur); resetBits();
+                codeSkipAndPredMode();
                 c->partSize(U(cuX, cuY), depth, size);
                 nj.frac_start[0] = c->fracBits;
-                load(cur);
+                load(*c, cur);
             }
             auto seen = [&](int x, int y, bool aboveOne) -> uint8_t {       /* getIntraDirLumaPredictor's view of a neighbour outside the CU (cudata.cpp:910-953) */
                 const x265amd_cu_unit* u = aboveOne ? ((y & 63) ? c->at(x >> 2, (y >> 2) - 1) : nullptr) : c->at((x >> 2) - 1, y >> 2);
@@ -583,9 +596,8 @@ struct IntraRd
                 x265amd_intra_nxn_job nj;
                 /* the NxN command first, on the second queue, when the caller has announced that mode's tiles (an 8x8 CU of an I picture): everything this queue has
                  * written is out (synchronised: a signalling command releases), the other workgroup looks (acquire) */
-                const uint32_t loN = (uint32_t)log2 - (uint32_t)(si->tu_max_depth_intra - 1 + 1);           /* the NxN call's transform range, as intra_cu_impl will find it */
-                const int rangeN0 = loN < (uint32_t)si->tu_log2_min ? si->tu_log2_min : (loN > (uint32_t)si->tu_log2_max ? si->tu_log2_max : (int)loN);
-                const bool goAhead = partSize == 0 && helper && hintPred && hintRecon && rangeN0 == 2 && 2 + rdLevel + ((depth + 1) >> 1) <= MAX_JOBS && dCand2.p;
+                /* (tuRangeMin(3): the NxN call's transform range, as its bind() will find it) */
+                const bool goAhead = partSize == 0 && helper && hintPred && hintRecon && tuRangeMin(3) == 2 && 2 + rdLevel + ((depth + 1) >> 1) <= MAX_JOBS && dCand2.p;
                 if (goAhead)
                 {
                     const uint8_t keep = U(cuX, cuY).part_size;
@@ -624,7 +636,7 @@ struct IntraRd
                 const uint32_t bm = nxn.mode[puIdx];
                 if (bm > 34) return fail("intra rd: NxN mode");
                 for (int yy = 0; yy < tuSize; yy += 4) for (int xx = 0; xx < tuSize; xx += 4) U(px + xx, py + yy).luma_dir = (uint8_t)bm;
-                load(cur);
+                load(*c, cur);
                 Cost ic = { 0, 0, 0, 0 };
                 pre = Pre{ true, px, py, log2TrSize, nxn.res[puIdx], log2TrSize > 3 ? curLevels : &nxn.levels[0][0] + 16 * puIdx, 0, 0, false };
                 const int rq = codeIntraLumaQT(px, py, initTuDepth, true, ic);
@@ -646,16 +658,13 @@ struct IntraRd
                 xa_phase(XA_PH_INTRA_CAND);
                 uint32_t preds[3];
                 c->lumaPreds(px, py, preds);
-                const uint64_t frac = cur.frac & 32767;
-                const uint8_t adi = cur.ctx[C_ADI];
                 x265amd_intra_pu_job pj;
                 memset(&pj, 0, sizeof(pj));
                 const uint64_t slot0 = (uint64_t)(uintptr_t)dCand.p;
                 fillJob(pj.tmpl, 0, px, py, log2TrSize, 0, slot0 + 1024 * isz, tuSize, slot0, tuSize, 0);
                 pj.tmpl.avail = available(px, py, tuSize);
                 pj.lambda = lambda;
-                pj.rbits = (uint32_t)((frac + k_bits[adi ^ 0]) >> 15) + 5;           /* as lumaScan below: bitsIntraModeNonMPM / bitsIntraModeMPM */
-                pj.mpm_base = (uint32_t)((frac + k_bits[adi ^ 1]) >> 15);
+                pj.rbits = nonMpmBits(); pj.mpm_base = mpmBaseBits();
                 pj.slot_pixels = 2048; pj.slot_coeffs = 1024;
                 for (int i = 0; i < 3; i++) pj.preds[i] = (uint8_t)preds[i];
                 pj.max_cand = (uint8_t)maxCandCount;
@@ -714,7 +723,7 @@ struct IntraRd
             int bestIdx = -1;
             for (int i = 0; i < numCand; i++)
             {
-                load(cur);
+                load(*c, cur);
                 for (int yy = 0; yy < tuSize; yy += 4) for (int xx = 0; xx < tuSize; xx += 4) U(px + xx, py + yy).luma_dir = (uint8_t)rdModeList[i];
                 Cost icosts = { 0, 0, 0, 0 };
                 if (batch)
@@ -728,7 +737,7 @@ struct IntraRd
                 if (icosts.rdcost < bcost) { bcost = icosts.rdcost; bmode = rdModeList[i]; bestIdx = i; }
             }
             for (int yy = 0; yy < tuSize; yy += 4) for (int xx = 0; xx < tuSize; xx += 4) U(px + xx, py + yy).luma_dir = (uint8_t)bmode;
-            load(cur);
+            load(*c, cur);
             Cost icosts = { 0, 0, 0, 0 };
             if (batch && bestIdx >= 0)
             {
@@ -747,7 +756,7 @@ struct IntraRd
             for (int q = 0; q < 4; q++) comb |= cbfBit(cuX + (q & 1) * half, cuY + (q >> 1) * half, 0, 1);
             U(cuX, cuY).cbf[0] |= (uint8_t)comb;
         }
-        load(cur);
+        load(*c, cur);
         return 0;
     }
 
@@ -869,7 +878,7 @@ struct IntraRd
             }
             coeffCBest[0] = coeffC[0]; coeffCBest[1] = coeffC[1];
             totalDistortion = dist;
-            load(cur);
+            load(*c, cur);
             return 0;
         }
         /* one chroma block per plane for the whole CU (no luma transform split, or an 8x8 CU): the five modes x two planes are independent
@@ -900,7 +909,7 @@ struct IntraRd
         }
         for (int k = 0; k < 5; k++)
         {
-            load(cur);
+            load(*c, cur);
             for (int yy = 0; yy < size; yy += 4) for (int xx = 0; xx < size; xx += 4) U(cuX + xx, cuY + yy).chroma_dir = (uint8_t)modeList[k];
             Cost outCost = { 0, 0, 0, 0 };
             if (single)
@@ -965,356 +974,351 @@ struct IntraRd
             xa_copy_rects(st, r4);
         }
         totalDistortion = bestDist;
-        load(cur);
+        load(*c, cur);
         return 0;
+    }
+    /* ---- binding a call to the working set ---- */
+    /* CUData::getIntraTUQtDepthRange (cudata.cpp:972-981): the smallest transform size of this CU coded 2Nx2N (partSize 0) or NxN */
+    int tuRangeMin(int partSize) const
+    {
+        /* unsigned in the reference: an 8x8 NxN CU with tu-intra-depth 4 wraps below zero and clips to the MAXIMUM size (no transform splits) */
+        const uint32_t lo = (uint32_t)log2 - (uint32_t)(si->tu_max_depth_intra - 1 + (partSize != 0));
+        return lo < (uint32_t)si->tu_log2_min ? si->tu_log2_min : (lo > (uint32_t)si->tu_log2_max ? si->tu_log2_max : (int)lo);
+    }
+    /* (the three pieces xa_intra_quad8_ws binds as well: the picture, a CU size with its QP, the lambdas and start contexts) */
+    void bindPicture(const IntraCall& a) { st = (hipStream_t)a.stream; si = a.si; rp = a.rp; units = a.units; w4 = si->pic_width >> 2; src = a.h_src; rec = a.h_rec; stride = a.stride; cstride = a.cstride; err = 0; }
+    void bindSize(int log2Size, int qp_) { log2 = log2Size; size = 1 << log2; depth = 6 - log2; qp = qp_; quantQps(qp, qpLumaScaled, qpChromaScaled); }
+    void bindCosts(int lambdaQp, const uint8_t* ctx, uint64_t frac)
+    {
+        setQP(lambdaQp, si->slice_type, rp->psy_rd);
+        memset(&cur, 0, sizeof(cur));
+        memcpy(cur.ctx, ctx, X265AMD_CTX_COUNT);
+        cur.frac = frac;
+    }
+    bool openCoder(CuScope& scope)
+    {
+        c = scope.coder = x265amd_cabac_open(si, units, 1);
+        if (c) c->ctuInProgress = true;          /* the analysis of a CTU asks (cabac_coder.h: lastQP) */
+        return c != nullptr;
+    }
+    bool allocMain()
+    {
+        if (dJobs.p) return true;
+        if (dJobs.alloc(sizeof(x265amd_intra_tu_job) * MAX_JOBS) == hipSuccess && dRes.alloc(sizeof(x265amd_tu_result) * MAX_JOBS) == hipSuccess &&
+            dCoeff.alloc((size_t)MAX_JOBS * 1024 * 2) == hipSuccess && dResi.alloc((size_t)MAX_JOBS * 1024 * 2) == hipSuccess &&
+            dCand.alloc((size_t)MAX_JOBS * 2048 * sizeof(pixel)) == hipSuccess && dLayer.alloc((size_t)4 * 4096 * sizeof(pixel)) == hipSuccess &&
+            dScan.alloc(35 * 4) == hipSuccess && dScanJob.alloc(sizeof(x265amd_intra_job)) == hipSuccess &&
+            dPuJob.alloc(sizeof(x265amd_intra_pu_job)) == hipSuccess && dPuOut.alloc(sizeof(x265amd_intra_pu_out)) == hipSuccess &&
+            dNxnJob.alloc(sizeof(x265amd_intra_nxn_job)) == hipSuccess && dNxnOut.alloc(sizeof(x265amd_intra_nxn_out)) == hipSuccess &&
+            dDevLevels.alloc(1024 * 2) == hipSuccess && dDevCLevels.alloc(2 * 256 * 2) == hipSuccess &&
+            dCoeffDev.alloc((size_t)MAX_JOBS * 1024 * 2 * 2) == hipSuccess &&
+            mCtx.alloc(X265AMD_CTX_STRIDE) == hipSuccess && mEstJob.alloc(sizeof(x265amd_est_job)) == hipSuccess &&
+            mRdoq.alloc(sizeof(x265amd_tu_rdoq) * MAX_JOBS) == hipSuccess && dEst.alloc(sizeof(x265amd_est_bits)) == hipSuccess)
+            return true;
+        dJobs.free();           /* a partly made working set is made again next time */
+        return false;
+    }
+    /* One CU of one call on this working set: everything the entry paths below need before their own work, in the order the queues see it.  partSize: how the CU's units
+     * start out.  pair: the caller is checkIntra, whose 2Nx2N and NxN calls for an 8x8 CU belong together -- the first keeps the NxN tiles the caller announced, the second
+     * collects the command the first started ahead.  scope: takes the coder and the CU's units as they were. */
+    int bind(const IntraCall& a, int partSize, bool pair, CuScope& scope)
+    {
+        const x265amd_rd_cu* cu = a.cu;
+        helper = xa_queue_helper(a.stream);
+        big[0].q = helper ? xa_queue_helper(helper) : nullptr;          /* the third queue rides on the second, the fourth on the third */
+        big[1].q = big[0].q ? xa_queue_helper(big[0].q) : nullptr;
+        if (ahead.on && !(pair && partSize == 3 && ahead.x == cu->x && ahead.y == cu->y))
+        {
+            /* a command started ahead that nobody came for: let it finish before anything else touches what it writes */
+            ahead.on = false;
+            if (xa_stream_sync(helper) != hipSuccess || xa_stream_fence(a.stream, XA_CMD_ACQUIRE) != hipSuccess) return xa_fail(X265AMD_EHIP, "intra rd: second queue");
+        }
+        if (!pair || partSize != 0 || cu->log2_size != 3) hintPred = hintRecon = 0;
+        haveWhole = false; haveNxn = false; haveDevChroma = false; lumaTileDone = false;
+        bindPicture(a);
+        cuX = cu->x; cuY = cu->y;
+        bindSize(cu->log2_size, cu->qp);
+        predTile = a.d_pred; reconTile = a.d_recon;
+        pre.on = false;
+        if (log2 < 3 || log2 > 5 || (cuX & (size - 1)) || (cuY & (size - 1)) || cuX < 0 || cuY < 0 || cuX + size > si->pic_width || cuY + size > si->pic_height)
+            return xa_fail(X265AMD_EINVAL, "intra rd: CU outside the picture, misaligned, or not 8..32");
+        range[0] = tuRangeMin(partSize); range[1] = si->tu_log2_max;
+        if (!allocMain()) return xa_fail(X265AMD_EHIP, "intra rd: out of device memory");
+        if (helper && !dCand2.p &&
+            (dCand2.alloc((size_t)MAX_JOBS * 2048 * sizeof(pixel)) != hipSuccess || dCoeffDev2.alloc((size_t)MAX_JOBS * 1024 * 2 * 2) != hipSuccess ||
+             dNxnJob2.alloc(sizeof(x265amd_intra_nxn_job)) != hipSuccess || dNxnOut2.alloc(sizeof(x265amd_intra_nxn_out)) != hipSuccess))
+            return xa_fail(X265AMD_EHIP, "intra rd: out of device memory");
+        for (int b = 0; b < 2; b++)
+            if (big[b].q && !big[b].cand.p && !big[b].alloc()) return xa_fail(X265AMD_EHIP, "intra rd: out of device memory");
+        if (rp->rdoq_level && xa_fill_async(st, dEst.p, 0, sizeof(x265amd_est_bits)) != hipSuccess)         /* the table is only read by RDOQ */
+            return xa_fail(X265AMD_EHIP, "intra rd: fill");
+        if (!openCoder(scope)) return xa_fail(X265AMD_EINVAL, "intra rd: slice description");
+        for (int l = 0; l < 4; l++) coeffL[l].assign(4096, 0);
+        for (int p = 0; p < 2; p++) { coeffC[p].assign(1024, 0); coeffCBest[p].assign(1024, 0); }
+        bindCosts(lambdaQpOf(*cu), cu->ctx, cu->frac_bits);
+        /* the CU as initSubCU + setPartSizeSubParts + setPredModeSubParts leave it */
+        scope.save(&units[(cuY >> 2) * w4 + (cuX >> 2)], w4, size >> 2);
+        for (int yy = 0; yy < scope.u4; yy++)
+            for (int xx = 0; xx < scope.u4; xx++)
+            {
+                x265amd_cu_unit& u = scope.row(yy)[xx];
+                memset(&u, 0, sizeof(u));
+                u.depth = (uint8_t)depth; u.pred_mode = X265AMD_MODE_INTRA; u.part_size = (uint8_t)partSize; u.luma_dir = 1; u.chroma_dir = 36; u.qp = (int8_t)qp;
+                u.ref_idx[0] = u.ref_idx[1] = -1;
+            }
+        return X265AMD_OK;
+    }
+
+    /* ---- the entry paths: one per job, each behind bind() ---- */
+    /* `g`'s command for this CU goes to g's queue behind everything this queue holds so far; `what` names the step in an error */
+    int startAhead(Big& g, const x265amd_intra_nxn_job& nj, const char* what)
+    {
+        memcpy(g.job.p, &nj, sizeof(nj));
+        if (xa_queue_follow(g.q, st) != hipSuccess || x265amd_intra_nxn(g.q, (const x265amd_intra_nxn_job*)g.job.p, (x265amd_intra_nxn_out*)g.out.p) != X265AMD_OK)
+            return xa_fail(X265AMD_EHIP, what);
+        g.on = true; g.x = cuX; g.y = cuY;
+        return 1;
+    }
+    /* Only starts the 2Nx2N command of a 16x16 / 32x32 CU of an I picture, on the third / fourth queue: the caller recurses into the sub-CUs and comes back with the
+     * ordinary call, which collects it.  1: started, 0: not possible here. */
+    int startLargeAhead()
+    {
+        Big& g = big[log2 == 5 ? 1 : 0];
+        static const bool devRdoq = xa_env_on("X265AMD_DEVICE_RDOQ");
+        if (!((log2 == 4 || log2 == 5) && g.q && g.cand.p && !g.on && (!rp->rdoq_level || devRdoq) && range[0] == log2 && range[1] >= log2 &&
+              2 + rp->rd_level + (depth >> 1) <= MAX_JOBS))
+            return 0;
+        x265amd_intra_nxn_job nj;
+        buildDevJob(nj, 0, rp->rd_level, predTile, reconTile, (uint64_t)(uintptr_t)g.cand.p, (uint64_t)(uintptr_t)g.coeffDev.p, g.levels.p, g.clevels.p);
+        nj.no_picture = 1;
+        return startAhead(g, nj, "intra rd: large unit step ahead");
+    }
+    /* Only starts the intra try of a P / B CU, on the queue of its depth.  1: started, 0: not possible here. */
+    /* Round 3 measured it 1-4 % slower (what the try hides, 40 us of device time per CU that gets to it, was eaten by
+     * what starting it costs every unskipped CU); since round 4 the CUs that end as skips never get here -- the device's skip chain ends them (inter_chain_dev.h) -- and
+     * a CU that does is searched, predicted and coded while its intra try runs beside: 35.8 -> 40.9 frames/s on the bench clip */
+    int startTryAhead()
+    {
+        Big& g = inter[5 - log2];
+        if (!devIntraInInter()) return 0;
+        if (xa_is_queue(st))
+        {
+            /* the queue of this depth: taken when the first CU of the CTU wants it (never waiting for one), given back with the CTU's working set */
+            if (!g.q) { g.q = xa_queue_try_acquire(); g.owned = g.q != nullptr; }
+            if (g.q && !g.cand.p && !g.alloc()) return xa_fail(X265AMD_EHIP, "intra rd: out of device memory");
+        }
+        if (!g.q || !g.cand.p) return 0;
+        if (g.on) { g.on = false; if (xa_stream_sync(g.q) != hipSuccess) return xa_fail(X265AMD_EHIP, "intra rd: second queue"); }      /* an earlier try nobody collected */
+        x265amd_intra_nxn_job nj;
+        buildInInterJob(nj, predTile, reconTile, (uint64_t)(uintptr_t)g.cand.p, (uint64_t)(uintptr_t)g.coeffDev.p, g.levels.p, g.clevels.p);
+        return startAhead(g, nj, "intra rd: intra try ahead");
+    }
+    /* checkIntraInInter + encodeIntraInInter as one command, the mode picked on the device: collected when it was started ahead at the CU's entry, run here otherwise */
+    int tryOnDevice(uint64_t* info, sse_t& lumaDist)
+    {
+        Big& g = inter[5 - log2];
+        x265amd_intra_nxn_out nxn;
+        curLevels = (const int16_t*)dDevLevels.p; curCLevels = (const int16_t*)dDevCLevels.p;
+        if (g.on && g.x == cuX && g.y == cuY)
+        {
+            g.on = false;
+            if (xa_stream_sync(g.q) != hipSuccess || xa_stream_fence(st, XA_CMD_ACQUIRE) != hipSuccess) return xa_fail(X265AMD_EHIP, "intra rd: intra try");
+            memcpy(&nxn, g.out.p, sizeof(nxn));
+            curLevels = (const int16_t*)g.levels.p; curCLevels = (const int16_t*)g.clevels.p;
+        }
+        else
+        {
+            x265amd_intra_nxn_job nj;
+            buildInInterJob(nj, predTile, reconTile, (uint64_t)(uintptr_t)dCand.p, (uint64_t)(uintptr_t)dCoeffDev.p, nullptr, nullptr);
+            memcpy(dNxnJob.p, &nj, sizeof(nj));
+            if (x265amd_intra_nxn(st, (const x265amd_intra_nxn_job*)dNxnJob.p, (x265amd_intra_nxn_out*)dNxnOut.p) != X265AMD_OK || xa_stream_sync(st) != hipSuccess)
+                return xa_fail(X265AMD_EHIP, "intra rd: intra try");
+            memcpy(&nxn, dNxnOut.p, sizeof(nxn));
+        }
+        const uint32_t bmode = nxn.mode[0];
+        if (bmode > 34) return xa_fail(X265AMD_EHIP, "intra rd: intra try mode");
+        /* the mode's bits and cost as the scan prices them (loadIntraDirModeLuma + bitsIntraModeMPM / NonMPM) */
+        uint32_t preds[3];
+        c->lumaPreds(cuX, cuY, preds);
+        const uint32_t b = modeBits(preds, bmode), sad = nxn.chroma_reserved;
+        if (info) { info[0] = bmode; info[1] = calcRdSADCost(sad, b); info[2] = b; info[3] = sad; }
+        for (int yy = 0; yy < size; yy += 4) for (int xx = 0; xx < size; xx += 4) U(cuX + xx, cuY + yy).luma_dir = (uint8_t)bmode;
+        load(*c, cur);
+        Cost icosts = { 0, 0, 0, 0 };
+        pre = Pre{ true, cuX, cuY, log2, nxn.res[0], log2 > 3 ? curLevels : &nxn.levels[0][0], 0, 0, false };
+        const int rc = codeIntraLumaQT(cuX, cuY, 0, false, icosts) ? err : X265AMD_OK;
+        pre.on = false;
+        lumaDist = icosts.distortion;
+        haveDevChroma = true; lumaTileDone = true; nxnChroma = nxn;
+        return rc;
+    }
+    /* checkIntraInInter by the host's scan -- DC first, then planar, then the angular modes, strict improvement; --fast-intra samples them -- and encodeIntraInInter */
+    int tryByScan(uint64_t* info, sse_t& lumaDist)
+    {
+        uint64_t modeCosts[35]; uint32_t mb[35], ms[35];
+        if (lumaScan(cuX, cuY, log2, modeCosts, mb, ms)) return err;
+        static const uint8_t order[35] = { 1, 0, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23, 24, 25, 26, 27, 28, 29, 30, 31, 32, 33, 34 };
+        uint32_t bmode = 1;
+        if (rp->fast_intra)
+        {
+            /* the best angle sampled at distance 5, refined at distance 2 and 1 (search.cpp:1401-1434); DC / planar first as always */
+            if (modeCosts[0] < modeCosts[bmode]) bmode = 0;
+            uint32_t amode = 5;
+            uint64_t acost = kMaxCost;
+            for (uint32_t mode = 5; mode < 35; mode += 5) if (modeCosts[mode] < acost) { acost = modeCosts[mode]; amode = mode; }
+            for (uint32_t dist = 2; dist >= 1; dist--)
+            {
+                const uint32_t lowmode = amode - dist, highmode = amode + dist;
+                if (modeCosts[lowmode] < acost) { acost = modeCosts[lowmode]; amode = lowmode; }
+                if (modeCosts[highmode] < acost) { acost = modeCosts[highmode]; amode = highmode; }
+            }
+            if (amode == 33 && modeCosts[34] < acost) { acost = modeCosts[34]; amode = 34; }
+            if (acost < modeCosts[bmode]) bmode = amode;
+        }
+        else
+            for (int k = 1; k < 35; k++) if (modeCosts[order[k]] < modeCosts[bmode]) bmode = order[k];
+        if (info) { info[0] = bmode; info[1] = modeCosts[bmode]; info[2] = mb[bmode]; info[3] = ms[bmode]; }
+        for (int yy = 0; yy < size; yy += 4) for (int xx = 0; xx < size; xx += 4) U(cuX + xx, cuY + yy).luma_dir = (uint8_t)bmode;
+        /* ---- encodeIntraInInter ---- */
+        load(*c, cur);
+        Cost icosts = { 0, 0, 0, 0 };
+        const int rc = codeIntraLumaQT(cuX, cuY, 0, false, icosts);
+        lumaDist = icosts.distortion;
+        return rc;
+    }
+    /* The common end of the ordinary paths, behind the luma decision (rc: its outcome): chroma, the CU's bits, the result record, checkDQP, the levels, the decided units.
+     * plain: an entry without a working set, which returns with everything done. */
+    int finish(int rc, const CuScope& scope, const x265amd_rd_cu* cu, int partSize, sse_t lumaDist, x265amd_cu_unit* cu_units, x265amd_rd_result* out, int16_t* coeff_out, bool plain)
+    {
+        const int u4 = scope.u4;
+        const size_t isz = sizeof(pixel);
+        sse_t chromaDist = 0;
+        xa_phase(XA_PH_INTRA_CAND);
+        std::vector<int16_t> coeffCu(4096 + 2048, 0);
+        if (rc == X265AMD_OK)
+        {
+            extractLuma(cuX, cuY, 0, coeffCu.data());
+            if (!lumaTileDone) copy2D(reconTile, 64, rec[0] + ((uint64_t)cuY * stride + cuX) * isz, stride, size, size);
+            rc = estIntraPredChromaQT(chromaDist);
+        }
+        xa_phase(XA_PH_INTRA_CHROMA);
+        if (rc == X265AMD_OK)
+        {
+            memcpy(coeffCu.data() + 4096, coeffCBest[0].data(), sizeof(int16_t) * 1024);
+            memcpy(coeffCu.data() + 5120, coeffCBest[1].data(), sizeof(int16_t) * 1024);
+            x265amd_cu_unit& u0 = *scope.first;
+            resetBits();
+            const uint32_t skipFlagBits = codeSkipAndPredMode();
+            c->partSize(u0, depth, size);
+            c->predInfo(cuX, cuY, size, u0);
+            const uint32_t mvBits = bits() - skipFlagBits;
+            bool dqp = si->use_dqp != 0;
+            c->coeffCtu[0] = coeffCu.data(); c->coeffCtu[1] = coeffCu.data() + 4096; c->coeffCtu[2] = coeffCu.data() + 5120;
+            c->ctuX0 = cuX; c->ctuY0 = cuY;
+            c->transform(cuX, cuY, cuX, cuY, 0, log2, dqp, range);
+            memset(out, 0, sizeof(*out));
+            out->total_bits = bits(); out->mv_bits = mvBits; out->coeff_bits = out->total_bits - mvBits - skipFlagBits;
+            out->luma_distortion = (uint32_t)lumaDist; out->chroma_distortion = (uint32_t)chromaDist;
+            const sse_t distortion = lumaDist + chromaDist;
+            out->distortion = distortion;
+            /* psy energy of the reconstruction, residual energy of the prediction (luma) */
+            if (haveNxn && partSize != 0)
+            {
+                out->psy_energy = psyRd ? nxnPsy : 0;
+                out->res_energy = nxnRes;
+            }
+            else if (haveWhole && partSize == 0)
+            {
+                /* one transform unit = the CU: psyCost(fenc, recon) and sse(fenc, pred) of the luma block came with the unit's result (rdcost.h:114-117,
+                 * search.cpp:1279-1283 / :1486-1503 measure exactly these two) */
+                out->psy_energy = psyRd ? wholeRes.nz_energy : 0;
+                out->res_energy = (uint32_t)(sse_t)wholeRes.zero_dist;
+            }
+            else
+            {
+                /* reconstruction and prediction tile in one launch */
+                x265amd_rd_cu mc2[2] = { *cu, *cu };
+                x265amd_cu_measure m2[2];
+                const uint64_t both[2] = { reconTile, predTile };
+                if (x265amd_measure_tile_list(st, src, stride, cstride, mc2, 2, both, m2) != X265AMD_OK) rc = X265AMD_EHIP;
+                out->psy_energy = psyRd ? m2[0].psy : 0;
+                out->res_energy = (uint32_t)(sse_t)m2[1].sse[0];
+            }
+            out->rd_cost = cost(distortion, out->total_bits, out->psy_energy);
+            memcpy(out->ctx, c->ctx, X265AMD_CTX_COUNT);            /* Mode::contexts is stored before checkDQP codes into it */
+            out->frac_bits = c->fracBits;
+            /* checkDQP (search.cpp:3974-4003) */
+            if (si->use_dqp && depth <= si->max_cu_dqp_depth)
+            {
+                const bool rootCbf = u0.cbf[0] || u0.cbf[1] || u0.cbf[2];
+                if (rootCbf)
+                {
+                    if (rp->rd_level >= 3) { resetBits(); c->deltaQP(cuX, cuY); out->total_bits += bits(); memcpy(out->ctx, c->ctx, X265AMD_CTX_COUNT); out->frac_bits = c->fracBits; }
+                    else if (rp->rd_level == 2) out->total_bits++;
+                    out->rd_cost = cost(distortion, out->total_bits, out->psy_energy);
+                }
+                else
+                {
+                    const int8_t q = (int8_t)c->refQP(cuX, cuY);
+                    for (int yy = 0; yy < u4; yy++) for (int xx = 0; xx < u4; xx++) scope.row(yy)[xx].qp = q;
+                }
+            }
+            if (coeff_out) memcpy(coeff_out, coeffCu.data(), sizeof(int16_t) * (4096 + 2048));
+        }
+        for (int yy = 0; yy < u4; yy++) memcpy(&cu_units[(size_t)yy * u4], scope.row(yy), sizeof(x265amd_cu_unit) * u4);         /* the decided CU, before `scope` puts the caller's units back */
+        /* What is still pending are block copies into tiles and the picture; the commands of a stream / queue run in order, so whoever reads them next waits for
+         * them anyway.  A caller that keeps the working set (same stream, next CU) goes on at once; the plain entry points return with everything done. */
+        if (rc == X265AMD_OK && plain && xa_stream_sync(st) != hipSuccess) rc = xa_fail(X265AMD_EHIP, "intra rd: synchronize");
+        return rc;
     }
 };
 
 IntraRd::~IntraRd() { chain_block_put(qBlock); }
 
+/* The working set of a call: the caller's (*ws; made at its first call, released by xa_intra_ws_free), or one that lives for this call when the caller keeps none. */
+struct WsRef
+{
+    IntraRd* ip; const bool own;
+    explicit WsRef(void** ws) : ip(ws && *ws ? static_cast<IntraRd*>(*ws) : new IntraRd), own(!ws) { if (ws) *ws = ip; }
+    ~WsRef() { if (own) delete ip; }
+};
+
 } // namespace
 
-/* shared body: kind 0 = checkIntraInInter + encodeIntraInInter, kind 1 = checkIntra(part_size) */
-/* ws (optional): where the caller keeps this routine's working set between calls -- the CUs of one CTU on one stream / queue use the same buffers
- * one after the other (xa_intra_ws_free releases it) */
-static int intra_cu_impl(int kind, int partSize, void* stream, const x265amd_slice_info* si, const x265amd_rd_params* rp, x265amd_cu_unit* units,
-                         const uint64_t* h_src, const uint64_t* h_rec, intptr_t stride, intptr_t cstride, const x265amd_rd_cu* cu,
-                         x265amd_cu_unit* cu_units, uint64_t d_pred, uint64_t d_recon, x265amd_rd_result* out, int16_t* coeff_out, uint64_t* info, void** ws = nullptr)
+/* An ordinary call: the refusals, the CU bound to the working set, the entry's own luma decision (`luma`), the common finish. */
+template <class Luma>
+static int intra_cu(const IntraCall& a, int partSize, bool pair, x265amd_cu_unit* cu_units, x265amd_rd_result* out, int16_t* coeff_out, void** ws, Luma luma)
 {
-    if (!si || !rp || !units || !h_src || !h_rec || !cu || (kind < 2 && (!cu_units || !out)) || !d_pred || !d_recon) return xa_fail(X265AMD_EINVAL, "intra rd: null argument");
-    if (si->tq_bypass_enabled) return xa_fail(X265AMD_EINVAL, "intra rd: lossless coding is not supported");
-    if (partSize != 0 && (partSize != 3 || cu->log2_size != 3 || si->tu_log2_min > 2)) return xa_fail(X265AMD_EINVAL, "intra rd: NxN only for 8x8 CUs with 4x4 transforms");
+    int rc = a.refuse(!cu_units || !out, partSize);
+    if (rc != X265AMD_OK) return rc;
     xa_phase(XA_PH_ANALYZER);
-    IntraRd* ip = ws && *ws ? static_cast<IntraRd*>(*ws) : new IntraRd;
-    if (ws) *ws = ip;
-    IntraRd& R = *ip;
-    R.helper = xa_queue_helper(stream);
-    R.big[0].q = R.helper ? xa_queue_helper(R.helper) : nullptr;          /* the third queue rides on the second, the fourth on the third */
-    R.big[1].q = R.big[0].q ? xa_queue_helper(R.big[0].q) : nullptr;
-    if (R.ahead.on && !(kind == 1 && partSize == 3 && R.ahead.x == cu->x && R.ahead.y == cu->y))
     {
-        /* a command started ahead that nobody came for: let it finish before anything else touches what it writes */
-        R.ahead.on = false;
-        if (xa_stream_sync(R.helper) != hipSuccess || xa_stream_fence(stream, XA_CMD_ACQUIRE) != hipSuccess) return xa_fail(X265AMD_EHIP, "intra rd: second queue");
+        WsRef w(ws);
+        CuScope scope;
+        if ((rc = w.ip->bind(a, partSize, pair, scope)) != X265AMD_OK) return rc;
+        sse_t lumaDist = 0;
+        xa_phase(XA_PH_INTRA_SETUP);
+        rc = luma(*w.ip, lumaDist);
+        rc = w.ip->finish(rc, scope, a.cu, partSize, lumaDist, cu_units, out, coeff_out, !ws);
     }
-    if (kind != 1 || partSize != 0 || cu->log2_size != 3) R.hintPred = R.hintRecon = 0;
-    R.haveWhole = false; R.haveNxn = false; R.haveDevChroma = false; R.lumaTileDone = false;
-    R.st = (hipStream_t)stream; R.si = si; R.rp = rp; R.units = units; R.w4 = si->pic_width >> 2; R.src = h_src; R.rec = h_rec; R.stride = stride; R.cstride = cstride;
-    R.cuX = cu->x; R.cuY = cu->y; R.log2 = cu->log2_size; R.size = 1 << R.log2; R.depth = 6 - R.log2; R.qp = cu->qp; R.err = 0;
-    R.predTile = d_pred; R.reconTile = d_recon;
-    R.pre.on = false;
-    int rc = X265AMD_OK;
-    if (R.log2 < 3 || R.log2 > 5 || (R.cuX & (R.size - 1)) || (R.cuY & (R.size - 1)) || R.cuX < 0 || R.cuY < 0 || R.cuX + R.size > si->pic_width || R.cuY + R.size > si->pic_height)
-        rc = xa_fail(X265AMD_EINVAL, "intra rd: CU outside the picture, misaligned, or not 8..32");
-    static const uint8_t chromaScale[58] = { 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23, 24, 25, 26, 27, 28, 29, 29, 30, 31,
-                                             32, 33, 33, 34, 34, 35, 35, 36, 36, 37, 37, 38, 39, 40, 41, 42, 43, 44, 45, 46, 47, 48, 49, 50, 51 };
-    const int bd = 6 * (X265AMD_DEPTH - 8);
-    const int qpQuant = R.qp < 0 ? 0 : (R.qp > 51 ? 51 : R.qp);
-    int qpC = qpQuant > 57 ? 57 : qpQuant;
-    if (qpC >= 30) qpC = chromaScale[qpC];
-    R.qpLumaScaled = qpQuant + bd; R.qpChromaScaled = qpC + bd;
-    /* CUData::getIntraTUQtDepthRange (cudata.cpp:972-981) */
-    {
-        /* unsigned in the reference: an 8x8 NxN CU with tu-intra-depth 4 wraps below zero and clips to the MAXIMUM size (no transform splits) */
-        const uint32_t lo = (uint32_t)R.log2 - (uint32_t)(si->tu_max_depth_intra - 1 + (partSize != 0));
-        R.range[0] = lo < (uint32_t)si->tu_log2_min ? si->tu_log2_min : (lo > (uint32_t)si->tu_log2_max ? si->tu_log2_max : (int)lo);
-        R.range[1] = si->tu_log2_max;
-    }
-    if (rc == X265AMD_OK && !R.dJobs.p &&
-        (R.dJobs.alloc(sizeof(x265amd_intra_tu_job) * IntraRd::MAX_JOBS) != hipSuccess || R.dRes.alloc(sizeof(x265amd_tu_result) * IntraRd::MAX_JOBS) != hipSuccess ||
-         R.dCoeff.alloc((size_t)IntraRd::MAX_JOBS * 1024 * 2) != hipSuccess || R.dResi.alloc((size_t)IntraRd::MAX_JOBS * 1024 * 2) != hipSuccess ||
-         R.dCand.alloc((size_t)IntraRd::MAX_JOBS * 2048 * sizeof(pixel)) != hipSuccess || R.dLayer.alloc((size_t)4 * 4096 * sizeof(pixel)) != hipSuccess ||
-         R.dScan.alloc(35 * 4) != hipSuccess || R.dScanJob.alloc(sizeof(x265amd_intra_job)) != hipSuccess ||
-         R.dPuJob.alloc(sizeof(x265amd_intra_pu_job)) != hipSuccess || R.dPuOut.alloc(sizeof(x265amd_intra_pu_out)) != hipSuccess ||
-         R.dNxnJob.alloc(sizeof(x265amd_intra_nxn_job)) != hipSuccess || R.dNxnOut.alloc(sizeof(x265amd_intra_nxn_out)) != hipSuccess ||
-         R.dDevLevels.alloc(1024 * 2) != hipSuccess || R.dDevCLevels.alloc(2 * 256 * 2) != hipSuccess ||
-         R.dCoeffDev.alloc((size_t)IntraRd::MAX_JOBS * 1024 * 2 * 2) != hipSuccess ||
-         R.mCtx.alloc(X265AMD_CTX_STRIDE) != hipSuccess || R.mEstJob.alloc(sizeof(x265amd_est_job)) != hipSuccess ||
-         R.mRdoq.alloc(sizeof(x265amd_tu_rdoq) * IntraRd::MAX_JOBS) != hipSuccess || R.dEst.alloc(sizeof(x265amd_est_bits)) != hipSuccess))
-    {
-        rc = xa_fail(X265AMD_EHIP, "intra rd: out of device memory");
-        R.dJobs.free();         /* a partly made working set is made again next time */
-    }
-    if (rc == X265AMD_OK && R.helper && !R.dCand2.p &&
-        (R.dCand2.alloc((size_t)IntraRd::MAX_JOBS * 2048 * sizeof(pixel)) != hipSuccess || R.dCoeffDev2.alloc((size_t)IntraRd::MAX_JOBS * 1024 * 2 * 2) != hipSuccess ||
-         R.dNxnJob2.alloc(sizeof(x265amd_intra_nxn_job)) != hipSuccess || R.dNxnOut2.alloc(sizeof(x265amd_intra_nxn_out)) != hipSuccess))
-        rc = xa_fail(X265AMD_EHIP, "intra rd: out of device memory");
-    for (int b = 0; b < 2 && rc == X265AMD_OK; b++)
-    {
-        IntraRd::Big& g = R.big[b];
-        if (g.q && !g.cand.p &&
-            (g.cand.alloc((size_t)IntraRd::MAX_JOBS * 2048 * sizeof(pixel)) != hipSuccess || g.coeffDev.alloc((size_t)IntraRd::MAX_JOBS * 1024 * 2 * 2) != hipSuccess ||
-             g.job.alloc(sizeof(x265amd_intra_nxn_job)) != hipSuccess || g.out.alloc(sizeof(x265amd_intra_nxn_out)) != hipSuccess ||
-             g.levels.alloc(1024 * 2) != hipSuccess || g.clevels.alloc(2 * 256 * 2) != hipSuccess))
-            rc = xa_fail(X265AMD_EHIP, "intra rd: out of device memory");
-    }
-    if (rc == X265AMD_OK && rp->rdoq_level && xa_fill_async(R.st, R.dEst.p, 0, sizeof(x265amd_est_bits)) != hipSuccess)         /* the table is only read by RDOQ */
-        rc = xa_fail(X265AMD_EHIP, "intra rd: fill");
-    x265amd_cabac* coder = rc == X265AMD_OK ? x265amd_cabac_open(si, units, 1) : nullptr;
-    if (coder) coder->ctuInProgress = true;          /* the analysis of a CTU asks (cabac_coder.h: lastQP) */
-    if (rc == X265AMD_OK && !coder) rc = xa_fail(X265AMD_EINVAL, "intra rd: slice description");
-    if (rc != X265AMD_OK) { if (coder) x265amd_cabac_close(coder); if (!ws) delete ip; return rc; }
-    R.c = coder;
-    for (int l = 0; l < 4; l++) R.coeffL[l].assign(4096, 0);
-    for (int p = 0; p < 2; p++) { R.coeffC[p].assign(1024, 0); R.coeffCBest[p].assign(1024, 0); }
-    uint64_t rd[6];
-    x265amd_rdcost(cu->reserved[0] ? (int)cu->reserved[0] : R.qp, si->slice_type, rp->psy_rd, 0, 0, 0, rd);          /* (the lambdas' QP: x265amd_rd_cu.reserved[0] above 51) */
-    R.lambda2 = rd[0]; R.lambda = rd[1]; R.psyRd = (uint32_t)rd[2];
-    memset(&R.cur, 0, sizeof(R.cur));
-    memcpy(R.cur.ctx, cu->ctx, X265AMD_CTX_COUNT);
-    R.cur.frac = cu->frac_bits;
-    const int w4 = R.w4, u4 = R.size >> 2;
-    std::vector<x265amd_cu_unit> saved((size_t)u4 * u4);
-    for (int yy = 0; yy < u4; yy++) memcpy(&saved[(size_t)yy * u4], &units[((R.cuY >> 2) + yy) * w4 + (R.cuX >> 2)], sizeof(x265amd_cu_unit) * u4);
-    const size_t isz = sizeof(pixel);
-    /* the CU as initSubCU + setPartSizeSubParts + setPredModeSubParts leave it */
-    for (int yy = 0; yy < u4; yy++)
-        for (int xx = 0; xx < u4; xx++)
-        {
-            x265amd_cu_unit& u = units[((R.cuY >> 2) + yy) * w4 + (R.cuX >> 2) + xx];
-            memset(&u, 0, sizeof(u));
-            u.depth = (uint8_t)R.depth; u.pred_mode = X265AMD_MODE_INTRA; u.part_size = (uint8_t)partSize; u.luma_dir = 1; u.chroma_dir = 36; u.qp = (int8_t)R.qp;
-            u.ref_idx[0] = u.ref_idx[1] = -1;
-        }
-    if (kind == 3)
-    {
-        int started = 0;
-        /* Round 3 measured it 1-4 % slower (what the try hides, 40 us of device time per CU that gets to it, was eaten by
-         * what starting it costs every unskipped CU); since round 4 the CUs that end as skips never get here -- the device's skip chain ends them (inter_chain_dev.h) -- and
-         * a CU that does is searched, predicted and coded while its intra try runs beside: 35.8 -> 40.9 frames/s on the bench clip */
-        IntraRd::Big& g = R.inter[R.log2 >= 3 && R.log2 <= 5 ? 5 - R.log2 : 0];
-        if (R.log2 >= 3 && R.log2 <= 5 && R.devIntraInInter() && xa_is_queue(R.st))
-        {
-            /* the queue of this depth: taken when the first CU of the CTU wants it (never waiting for one), given back with the CTU's working set */
-            if (!g.q) { g.q = xa_queue_try_acquire(); g.owned = g.q != nullptr; }
-            if (g.q && !g.cand.p &&
-                (g.cand.alloc((size_t)IntraRd::MAX_JOBS * 2048 * sizeof(pixel)) != hipSuccess || g.coeffDev.alloc((size_t)IntraRd::MAX_JOBS * 1024 * 2 * 2) != hipSuccess ||
-                 g.job.alloc(sizeof(x265amd_intra_nxn_job)) != hipSuccess || g.out.alloc(sizeof(x265amd_intra_nxn_out)) != hipSuccess ||
-                 g.levels.alloc(1024 * 2) != hipSuccess || g.clevels.alloc(2 * 256 * 2) != hipSuccess))
-                rc = xa_fail(X265AMD_EHIP, "intra rd: out of device memory");
-        }
-        if (rc == X265AMD_OK && R.log2 >= 3 && R.log2 <= 5 && g.q && g.cand.p && R.devIntraInInter())
-        {
-            if (g.on) { g.on = false; if (xa_stream_sync(g.q) != hipSuccess) rc = xa_fail(X265AMD_EHIP, "intra rd: second queue"); }      /* an earlier try nobody collected */
-            if (rc == X265AMD_OK)
-            {
-                x265amd_intra_nxn_job nj;
-                R.buildInInterJob(nj, d_pred, d_recon, (uint64_t)(uintptr_t)g.cand.p, (uint64_t)(uintptr_t)g.coeffDev.p, g.levels.p, g.clevels.p);
-                memcpy(g.job.p, &nj, sizeof(nj));
-                if (xa_queue_follow(g.q, R.st) != hipSuccess ||
-                    x265amd_intra_nxn(g.q, (const x265amd_intra_nxn_job*)g.job.p, (x265amd_intra_nxn_out*)g.out.p) != X265AMD_OK)
-                    rc = xa_fail(X265AMD_EHIP, "intra rd: intra try ahead");
-                else { g.on = true; g.x = R.cuX; g.y = R.cuY; started = 1; }
-            }
-        }
-        for (int yy = 0; yy < u4; yy++) memcpy(&units[((R.cuY >> 2) + yy) * w4 + (R.cuX >> 2)], &saved[(size_t)yy * u4], sizeof(x265amd_cu_unit) * u4);
-        x265amd_cabac_close(coder);
-        return rc != X265AMD_OK ? rc : (started ? 1 : 0);
-    }
-    if (kind == 2)
-    {
-        /* only start the CU's 2Nx2N command (a 16x16 CU of an I picture, the third queue): the caller recurses into the sub-CUs and comes back with the ordinary call */
-        int started = 0;
-        IntraRd::Big& g = R.big[R.log2 == 5 ? 1 : 0];
-        static const bool devRdoq = xa_env_on("X265AMD_DEVICE_RDOQ");
-        if ((R.log2 == 4 || R.log2 == 5) && g.q && g.cand.p && !g.on && (!rp->rdoq_level || devRdoq) && R.range[0] == R.log2 && R.range[1] >= R.log2 &&
-            2 + rp->rd_level + (R.depth >> 1) <= IntraRd::MAX_JOBS)
-        {
-            x265amd_intra_nxn_job nj;
-            R.buildDevJob(nj, 0, rp->rd_level, d_pred, d_recon, (uint64_t)(uintptr_t)g.cand.p, (uint64_t)(uintptr_t)g.coeffDev.p, g.levels.p, g.clevels.p);
-            nj.no_picture = 1;
-            memcpy(g.job.p, &nj, sizeof(nj));
-            if (xa_queue_follow(g.q, R.st) != hipSuccess ||
-                x265amd_intra_nxn(g.q, (const x265amd_intra_nxn_job*)g.job.p, (x265amd_intra_nxn_out*)g.out.p) != X265AMD_OK)
-                rc = xa_fail(X265AMD_EHIP, "intra rd: large unit step ahead");
-            else { g.on = true; g.x = R.cuX; g.y = R.cuY; started = 1; }
-        }
-        for (int yy = 0; yy < u4; yy++) memcpy(&units[((R.cuY >> 2) + yy) * w4 + (R.cuX >> 2)], &saved[(size_t)yy * u4], sizeof(x265amd_cu_unit) * u4);
-        x265amd_cabac_close(coder);
-        return rc != X265AMD_OK ? rc : (started ? 1 : 0);
-    }
-    Cost icosts = { 0, 0, 0, 0 };
-    sse_t lumaDist = 0, chromaDist = 0;
-    xa_phase(XA_PH_INTRA_SETUP);
-    if (kind == 0 && R.devIntraInInter())
-    {
-        /* ---- checkIntraInInter + encodeIntraInInter as one command, the mode picked on the device; started ahead at the CU's entry when a queue was to spare ---- */
-        IntraRd::Big& g = R.inter[5 - R.log2];
-        x265amd_intra_nxn_out nxn;
-        const bool mineAhead = g.on && g.x == R.cuX && g.y == R.cuY;
-        R.curLevels = (const int16_t*)R.dDevLevels.p; R.curCLevels = (const int16_t*)R.dDevCLevels.p;
-        if (mineAhead)
-        {
-            g.on = false;
-            if (xa_stream_sync(g.q) != hipSuccess || xa_stream_fence(R.st, XA_CMD_ACQUIRE) != hipSuccess) rc = xa_fail(X265AMD_EHIP, "intra rd: intra try");
-            memcpy(&nxn, g.out.p, sizeof(nxn));
-            R.curLevels = (const int16_t*)g.levels.p; R.curCLevels = (const int16_t*)g.clevels.p;
-        }
-        else
-        {
-            x265amd_intra_nxn_job nj;
-            R.buildInInterJob(nj, d_pred, d_recon, (uint64_t)(uintptr_t)R.dCand.p, (uint64_t)(uintptr_t)R.dCoeffDev.p, nullptr, nullptr);
-            memcpy(R.dNxnJob.p, &nj, sizeof(nj));
-            if (x265amd_intra_nxn(R.st, (const x265amd_intra_nxn_job*)R.dNxnJob.p, (x265amd_intra_nxn_out*)R.dNxnOut.p) != X265AMD_OK || xa_stream_sync(R.st) != hipSuccess)
-                rc = xa_fail(X265AMD_EHIP, "intra rd: intra try");
-            memcpy(&nxn, R.dNxnOut.p, sizeof(nxn));
-        }
-        if (rc == X265AMD_OK)
-        {
-            const uint32_t bmode = nxn.mode[0];
-            if (bmode > 34) rc = xa_fail(X265AMD_EHIP, "intra rd: intra try mode");
-            else
-            {
-                /* the mode's bits and cost as the scan prices them (loadIntraDirModeLuma + bitsIntraModeMPM / NonMPM) */
-                uint32_t preds[3];
-                R.c->lumaPreds(R.cuX, R.cuY, preds);
-                const uint64_t frac = R.cur.frac & 32767;
-                const uint8_t adi = R.cur.ctx[C_ADI];
-                uint32_t b = (uint32_t)((frac + k_bits[adi ^ 0]) >> 15) + 5;
-                const uint32_t mpmBase = (uint32_t)((frac + k_bits[adi ^ 1]) >> 15);
-                for (int i = 0; i < 3; i++) if (preds[i] == bmode) { b = mpmBase + (bmode == preds[0] ? 1u : 2u); break; }
-                const uint32_t sad = nxn.chroma_reserved;
-                if (info) { info[0] = bmode; info[1] = R.calcRdSADCost(sad, b); info[2] = b; info[3] = sad; }
-                for (int yy = 0; yy < R.size; yy += 4) for (int xx = 0; xx < R.size; xx += 4) R.U(R.cuX + xx, R.cuY + yy).luma_dir = (uint8_t)bmode;
-                R.load(R.cur);
-                R.pre = IntraRd::Pre{ true, R.cuX, R.cuY, R.log2, nxn.res[0], R.log2 > 3 ? R.curLevels : &nxn.levels[0][0], 0, 0, false };
-                rc = R.codeIntraLumaQT(R.cuX, R.cuY, 0, false, icosts) ? R.err : X265AMD_OK;
-                R.pre.on = false;
-                lumaDist = icosts.distortion;
-                R.haveDevChroma = true; R.lumaTileDone = true; R.nxnChroma = nxn;
-            }
-        }
-    }
-    else if (kind == 0)
-    {
-        /* ---- checkIntraInInter: DC first, then planar, then the angular modes, strict improvement ---- */
-        uint64_t modeCosts[35]; uint32_t mb[35], ms[35];
-        rc = R.lumaScan(R.cuX, R.cuY, R.log2, modeCosts, mb, ms);
-        if (rc == X265AMD_OK)
-        {
-            static const uint8_t order[35] = { 1, 0, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23, 24, 25, 26, 27, 28, 29, 30, 31, 32, 33, 34 };
-            uint32_t bmode = 1;
-            if (rp->fast_intra)
-            {
-                /* the best angle sampled at distance 5, refined at distance 2 and 1 (search.cpp:1401-1434); DC / planar first as always */
-                if (modeCosts[0] < modeCosts[bmode]) bmode = 0;
-                uint32_t amode = 5;
-                uint64_t acost = kMaxCost;
-                for (uint32_t mode = 5; mode < 35; mode += 5) if (modeCosts[mode] < acost) { acost = modeCosts[mode]; amode = mode; }
-                for (uint32_t dist = 2; dist >= 1; dist--)
-                {
-                    const uint32_t lowmode = amode - dist, highmode = amode + dist;
-                    if (modeCosts[lowmode] < acost) { acost = modeCosts[lowmode]; amode = lowmode; }
-                    if (modeCosts[highmode] < acost) { acost = modeCosts[highmode]; amode = highmode; }
-                }
-                if (amode == 33 && modeCosts[34] < acost) { acost = modeCosts[34]; amode = 34; }
-                if (acost < modeCosts[bmode]) bmode = amode;
-            }
-            else
-                for (int k = 1; k < 35; k++) if (modeCosts[order[k]] < modeCosts[bmode]) bmode = order[k];
-            if (info) { info[0] = bmode; info[1] = modeCosts[bmode]; info[2] = mb[bmode]; info[3] = ms[bmode]; }
-            for (int yy = 0; yy < R.size; yy += 4) for (int xx = 0; xx < R.size; xx += 4) R.U(R.cuX + xx, R.cuY + yy).luma_dir = (uint8_t)bmode;
-            /* ---- encodeIntraInInter ---- */
-            R.load(R.cur);
-            rc = R.codeIntraLumaQT(R.cuX, R.cuY, 0, false, icosts);
-            lumaDist = icosts.distortion;
-        }
-    }
-    else
-        rc = R.estIntraPredQT(partSize, rp->rd_level, lumaDist);
-    xa_phase(XA_PH_INTRA_CAND);
-    std::vector<int16_t> coeffCu(4096 + 2048, 0);
-    if (rc == X265AMD_OK)
-    {
-        R.extractLuma(R.cuX, R.cuY, 0, coeffCu.data());
-        if (!R.lumaTileDone) R.copy2D(d_recon, 64, h_rec[0] + ((uint64_t)R.cuY * stride + R.cuX) * isz, stride, R.size, R.size);
-        rc = R.estIntraPredChromaQT(chromaDist);
-    }
-    xa_phase(XA_PH_INTRA_CHROMA);
-    if (rc == X265AMD_OK)
-    {
-        memcpy(coeffCu.data() + 4096, R.coeffCBest[0].data(), sizeof(int16_t) * 1024);
-        memcpy(coeffCu.data() + 5120, R.coeffCBest[1].data(), sizeof(int16_t) * 1024);
-        x265amd_cu_unit& u0 = units[(R.cuY >> 2) * w4 + (R.cuX >> 2)];
-        R.resetBits();
-        uint32_t skipFlagBits = 0;
-        if (si->slice_type != 2)
-        {
-            const x265amd_cu_unit* l = coder->at((R.cuX >> 2) - 1, R.cuY >> 2);
-            const x265amd_cu_unit* a = coder->at(R.cuX >> 2, (R.cuY >> 2) - 1);
-            const int skipCtx = (x265amd_cabac::coded(l) && l->pred_mode == X265AMD_MODE_SKIP) + (x265amd_cabac::coded(a) && a->pred_mode == X265AMD_MODE_SKIP);
-            coder->bin(0, C_SKIP + skipCtx);
-            skipFlagBits = R.bits();
-            coder->bin(1, C_PRED_MODE);
-        }
-        coder->partSize(u0, R.depth, R.size);
-        coder->predInfo(R.cuX, R.cuY, R.size, u0);
-        const uint32_t mvBits = R.bits() - skipFlagBits;
-        bool dqp = si->use_dqp != 0;
-        coder->coeffCtu[0] = coeffCu.data(); coder->coeffCtu[1] = coeffCu.data() + 4096; coder->coeffCtu[2] = coeffCu.data() + 5120;
-        coder->ctuX0 = R.cuX; coder->ctuY0 = R.cuY;
-        coder->transform(R.cuX, R.cuY, R.cuX, R.cuY, 0, R.log2, dqp, R.range);
-        memset(out, 0, sizeof(*out));
-        out->total_bits = R.bits(); out->mv_bits = mvBits; out->coeff_bits = out->total_bits - mvBits - skipFlagBits;
-        out->luma_distortion = (uint32_t)lumaDist; out->chroma_distortion = (uint32_t)chromaDist;
-        const sse_t distortion = lumaDist + chromaDist;
-        out->distortion = distortion;
-        /* psy energy of the reconstruction, residual energy of the prediction (luma) */
-        x265amd_rd_cu mc2[2] = { *cu, *cu };
-        x265amd_cu_measure m2[2];
-        if (R.haveNxn && partSize != 0)
-        {
-            out->psy_energy = R.psyRd ? R.nxnPsy : 0;
-            out->res_energy = R.nxnRes;
-        }
-        else if (R.haveWhole && partSize == 0)
-        {
-            /* one transform unit = the CU: psyCost(fenc, recon) and sse(fenc, pred) of the luma block came with the unit's result (rdcost.h:114-117,
-             * search.cpp:1279-1283 / :1486-1503 measure exactly these two) */
-            out->psy_energy = R.psyRd ? R.wholeRes.nz_energy : 0;
-            out->res_energy = (uint32_t)(sse_t)R.wholeRes.zero_dist;
-        }
-        else
-        {
-            /* reconstruction and prediction tile in one launch */
-            const uint64_t both[2] = { d_recon, d_pred };
-            if (x265amd_measure_tile_list(stream, h_src, stride, cstride, mc2, 2, both, m2) != X265AMD_OK) rc = X265AMD_EHIP;
-            out->psy_energy = R.psyRd ? m2[0].psy : 0;
-            out->res_energy = (uint32_t)(sse_t)m2[1].sse[0];
-        }
-        out->rd_cost = R.cost(distortion, out->total_bits, out->psy_energy);
-        memcpy(out->ctx, coder->ctx, X265AMD_CTX_COUNT);            /* Mode::contexts is stored before checkDQP codes into it */
-        out->frac_bits = coder->fracBits;
-        /* checkDQP (search.cpp:3974-4003) */
-        if (si->use_dqp && R.depth <= si->max_cu_dqp_depth)
-        {
-            const bool rootCbf = u0.cbf[0] || u0.cbf[1] || u0.cbf[2];
-            if (rootCbf)
-            {
-                if (rp->rd_level >= 3) { R.resetBits(); coder->deltaQP(R.cuX, R.cuY); out->total_bits += R.bits(); memcpy(out->ctx, coder->ctx, X265AMD_CTX_COUNT); out->frac_bits = coder->fracBits; }
-                else if (rp->rd_level == 2) out->total_bits++;
-                out->rd_cost = R.cost(distortion, out->total_bits, out->psy_energy);
-            }
-            else
-            {
-                const int8_t q = (int8_t)coder->refQP(R.cuX, R.cuY);
-                for (int yy = 0; yy < u4; yy++) for (int xx = 0; xx < u4; xx++) units[((R.cuY >> 2) + yy) * w4 + (R.cuX >> 2) + xx].qp = q;
-            }
-        }
-        if (coeff_out) memcpy(coeff_out, coeffCu.data(), sizeof(int16_t) * (4096 + 2048));
-    }
-    for (int yy = 0; yy < u4; yy++)
-    {
-        memcpy(&cu_units[(size_t)yy * u4], &units[((R.cuY >> 2) + yy) * w4 + (R.cuX >> 2)], sizeof(x265amd_cu_unit) * u4);
-        memcpy(&units[((R.cuY >> 2) + yy) * w4 + (R.cuX >> 2)], &saved[(size_t)yy * u4], sizeof(x265amd_cu_unit) * u4);
-    }
-    /* What is still pending are block copies into tiles and the picture; the commands of a stream / queue run in order, so whoever reads them next waits for
-     * them anyway.  A caller that keeps the working set (same stream, next CU) goes on at once; the plain entry points return with everything done. */
-    if (rc == X265AMD_OK && !ws && xa_stream_sync(R.st) != hipSuccess) rc = xa_fail(X265AMD_EHIP, "intra rd: synchronize");
-    x265amd_cabac_close(coder);
-    if (!ws) delete ip;
     xa_phase(XA_PH_INTRA_FINAL);
     return rc;
+}
+/* x265amd_check_intra: Search::checkIntra(part_size) of one CU */
+int xa_check_intra_ws(void* stream, const x265amd_slice_info* si, const x265amd_rd_params* rp, x265amd_cu_unit* units, const uint64_t* h_src, const uint64_t* h_rec,
+                      intptr_t stride, intptr_t cstride, const x265amd_rd_cu* cu, int part_size, x265amd_cu_unit* cu_units, uint64_t d_pred, uint64_t d_recon,
+                      x265amd_rd_result* out, int16_t* coeff_out, void** ws)
+{
+    return intra_cu({ stream, si, rp, units, h_src, h_rec, stride, cstride, cu, d_pred, d_recon }, part_size, true, cu_units, out, coeff_out, ws,
+                    [&](IntraRd& R, sse_t& lumaDist) { return R.estIntraPredQT(part_size, rp->rd_level, lumaDist); });
+}
+/* x265amd_intra_in_inter: Search::checkIntraInInter + encodeIntraInInter of one CU */
+int xa_intra_in_inter_ws(void* stream, const x265amd_slice_info* si, const x265amd_rd_params* rp, x265amd_cu_unit* units, const uint64_t* h_src, const uint64_t* h_rec,
+                         intptr_t stride, intptr_t cstride, const x265amd_rd_cu* cu, x265amd_cu_unit* cu_units, uint64_t d_pred, uint64_t d_recon, x265amd_rd_result* out,
+                         int16_t* coeff_out, uint64_t* info, void** ws)
+{
+    return intra_cu({ stream, si, rp, units, h_src, h_rec, stride, cstride, cu, d_pred, d_recon }, 0, false, cu_units, out, coeff_out, ws,
+                    [&](IntraRd& R, sse_t& lumaDist) { return R.devIntraInInter() ? R.tryOnDevice(info, lumaDist) : R.tryByScan(info, lumaDist); });
 }
 
 /* The four 8x8 CUs of the 16x16 block at (x, y) of an I picture, decided on the device one after the other without the host between them (Analysis::compressIntraCU's
@@ -1344,28 +1348,10 @@ int xa_intra_quad8_ws(void* stream, const x265amd_slice_info* si, const x265amd_
             return xa_fail(X265AMD_EHIP, "intra rd: out of device memory");
     }
     XA_HOSTPROF("quad8 (all but the wait)");
-    R.st = (hipStream_t)stream; R.si = si; R.rp = rp; R.units = units; R.w4 = si->pic_width >> 2; R.src = h_src; R.rec = h_rec; R.stride = stride; R.cstride = cstride;
-    R.log2 = 3; R.size = 8; R.depth = 3; R.qp = qp; R.err = 0; R.helper = helper;
-    {
-        static const uint8_t chromaScale[58] = { 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23, 24, 25, 26, 27, 28, 29, 29, 30, 31,
-                                                 32, 33, 33, 34, 34, 35, 35, 36, 36, 37, 37, 38, 39, 40, 41, 42, 43, 44, 45, 46, 47, 48, 49, 50, 51 };
-        const int bd = 6 * (X265AMD_DEPTH - 8);
-        const int qpQuant = qp < 0 ? 0 : (qp > 51 ? 51 : qp);
-        int qpC = qpQuant > 57 ? 57 : qpQuant;
-        if (qpC >= 30) qpC = chromaScale[qpC];
-        R.qpLumaScaled = qpQuant + bd; R.qpChromaScaled = qpC + bd;
-    }
-    uint64_t rd[6];
-    x265amd_rdcost(lambda_qp > 0 ? lambda_qp : qp, si->slice_type, rp->psy_rd, 0, 0, 0, rd);
-    R.lambda2 = rd[0]; R.lambda = rd[1]; R.psyRd = (uint32_t)rd[2];
-    memset(&R.cur, 0, sizeof(R.cur));
-    memcpy(R.cur.ctx, ctx, X265AMD_CTX_COUNT);
-    R.cur.frac = frac;
-    x265amd_cabac* coder;
-    { XA_HOSTPROF("quad8 cabac_open"); coder = x265amd_cabac_open(si, units, 1); }
-    if (coder) coder->ctuInProgress = true;          /* the analysis of a CTU asks (cabac_coder.h: lastQP) */
-    if (!coder) return xa_fail(X265AMD_EINVAL, "intra rd: slice description");
-    R.c = coder;
+    R.helper = helper;
+    R.bindPicture({ stream, si, rp, units, h_src, h_rec, stride, cstride, nullptr, 0, 0 });
+    R.bindSize(3, qp);
+    R.bindCosts(lambda_qp > 0 ? lambda_qp : qp, ctx, frac);
     x265amd_intra_nxn_job* jobs = static_cast<x265amd_intra_nxn_job*>(R.qJobs.p);
     x265amd_intra_cu8_result* outs = static_cast<x265amd_intra_cu8_result*>(R.qOut.p);
     x265amd_intra_peer* peers = static_cast<x265amd_intra_peer*>(R.qBlock);
@@ -1374,60 +1360,65 @@ int xa_intra_quad8_ws(void* stream, const x265amd_slice_info* si, const x265amd_
     /* The chain's counts never repeat, in any chain of the process: records come from the pools, and a workgroup that looks at one may still hold (in its L2) what an
      * earlier chain left there -- an old count is smaller than every new one and only makes the reader look again. */
     static std::atomic<uint64_t> tokens{ 1 };
-    const uint64_t token0 = tokens.fetch_add(4);
-    for (int i = 0; i < 4; i++)
     {
-        R.cuX = x + 8 * (i & 1); R.cuY = y + 8 * (i >> 1);
-        /* the CU as initSubCU + setPredModeSubParts leave it (the caller writes the decided CU over it afterwards) */
-        for (int k = 0; k < 4; k++)
+        CuScope scope;          /* the coder of the records' making: no units to put back, the caller writes the decided CUs over them */
+        bool opened;
+        { XA_HOSTPROF("quad8 cabac_open"); opened = R.openCoder(scope); }
+        if (!opened) return xa_fail(X265AMD_EINVAL, "intra rd: slice description");
+        const uint64_t token0 = tokens.fetch_add(4);
+        for (int i = 0; i < 4; i++)
         {
-            x265amd_cu_unit& u = R.U(R.cuX + 4 * (k & 1), R.cuY + 4 * (k >> 1));
-            memset(&u, 0, sizeof(u));
-            u.depth = 3; u.pred_mode = X265AMD_MODE_INTRA; u.luma_dir = 1; u.chroma_dir = 36; u.qp = (int8_t)qp; u.ref_idx[0] = u.ref_idx[1] = -1;
-        }
-        x265amd_cu_unit& u0 = R.U(R.cuX, R.cuY);
-        const uint8_t keepPart = u0.part_size;
-        for (int role = 1; role <= 2; role++)
-        {
-            x265amd_intra_nxn_job nj;
-            const int partSize = role == 1 ? 3 : 0;
-            R.range[0] = partSize ? 2 : 3; R.range[1] = si->tu_log2_max;
-            u0.part_size = (uint8_t)partSize;
+            R.cuX = x + 8 * (i & 1); R.cuY = y + 8 * (i >> 1);
+            /* the CU as initSubCU + setPredModeSubParts leave it (the caller writes the decided CU over it afterwards) */
+            for (int k = 0; k < 4; k++)
             {
-            XA_HOSTPROF("quad8 buildDevJob");
-            if (role == 1) R.buildDevJob(nj, 3, rp->rd_level, tilesN[0], tilesN[1], (uint64_t)(uintptr_t)R.dCand.p, (uint64_t)(uintptr_t)R.dCoeffDev.p);
-            else R.buildDevJob(nj, 0, rp->rd_level, tiles2[0], tiles2[1], (uint64_t)(uintptr_t)R.dCand2.p, (uint64_t)(uintptr_t)R.dCoeffDev2.p);
+                x265amd_cu_unit& u = R.U(R.cuX + 4 * (k & 1), R.cuY + 4 * (k >> 1));
+                memset(&u, 0, sizeof(u));
+                u.depth = 3; u.pred_mode = X265AMD_MODE_INTRA; u.luma_dir = 1; u.chroma_dir = 36; u.qp = (int8_t)qp; u.ref_idx[0] = u.ref_idx[1] = -1;
             }
-            nj.no_picture = role == 2;
-            nj.chain = (uint64_t)(uintptr_t)chainRec; nj.peer = (uint64_t)(uintptr_t)&peers[i]; nj.cu_out = (uint64_t)(uintptr_t)&outs[i];
-            nj.chain_token = token0 + i; nj.chain_role = (uint8_t)role; nj.chain_first = i == 0; nj.chain_index = (uint8_t)i;
-            if (si->use_dqp)
+            x265amd_cu_unit& u0 = R.U(R.cuX, R.cuY);
+            const uint8_t keepPart = u0.part_size;
+            for (int role = 1; role <= 2; role++)
             {
-                /* Entropy::codeDeltaQP's value for the CUs of this block (entropy.cpp:1737-1756): the group's QP against its prediction, wrapped */
-                const int bd = 6 * (X265AMD_DEPTH - 8);
-                int dqp = qp - coder->refQP(x, y);
-                dqp = (dqp + 78 + bd + (bd / 2)) % (52 + bd) - 26 - (bd / 2);
-                nj.reserved[0] = 1; nj.reserved[1] = (uint8_t)(int8_t)dqp;
-            }
-            /* the neighbour modes inside the block are the chain's: left of units 0 / 2 = units 1 / 3 of the CU to the left, above of units 0 / 1 = units 2 / 3 of the CU above */
-            nj.mode_src[0] = (i & 1) ? (uint8_t)(((i - 1) << 2) | 1) : 0xFF; nj.mode_src[1] = (i & 1) ? (uint8_t)(((i - 1) << 2) | 3) : 0xFF;
-            nj.mode_src[2] = (i & 2) ? (uint8_t)(((i - 2) << 2) | 2) : 0xFF; nj.mode_src[3] = (i & 2) ? (uint8_t)(((i - 2) << 2) | 3) : 0xFF;
-            if (role == 1)
-            {
-                nj.peer_recon[0] = tiles2[1];
-                nj.win_dst[0] = split_recon + ((size_t)(8 * (i >> 1)) * 64 + 8 * (i & 1)) * isz;
-                for (int pl = 0; pl < 2; pl++)
+                x265amd_intra_nxn_job nj;
+                const int partSize = role == 1 ? 3 : 0;
+                R.range[0] = partSize ? 2 : 3; R.range[1] = si->tu_log2_max;
+                u0.part_size = (uint8_t)partSize;
                 {
-                    nj.peer_recon[1 + pl] = tiles2[1] + (4096 + (size_t)pl * 1024) * isz;
-                    nj.win_dst[1 + pl] = split_recon + (4096 + (size_t)pl * 1024 + (size_t)(4 * (i >> 1)) * 32 + 4 * (i & 1)) * isz;
+                XA_HOSTPROF("quad8 buildDevJob");
+                if (role == 1) R.buildDevJob(nj, 3, rp->rd_level, tilesN[0], tilesN[1], (uint64_t)(uintptr_t)R.dCand.p, (uint64_t)(uintptr_t)R.dCoeffDev.p);
+                else R.buildDevJob(nj, 0, rp->rd_level, tiles2[0], tiles2[1], (uint64_t)(uintptr_t)R.dCand2.p, (uint64_t)(uintptr_t)R.dCoeffDev2.p);
                 }
+                nj.no_picture = role == 2;
+                nj.chain = (uint64_t)(uintptr_t)chainRec; nj.peer = (uint64_t)(uintptr_t)&peers[i]; nj.cu_out = (uint64_t)(uintptr_t)&outs[i];
+                nj.chain_token = token0 + i; nj.chain_role = (uint8_t)role; nj.chain_first = i == 0; nj.chain_index = (uint8_t)i;
+                if (si->use_dqp)
+                {
+                    /* Entropy::codeDeltaQP's value for the CUs of this block (entropy.cpp:1737-1756): the group's QP against its prediction, wrapped */
+                    const int bd = 6 * (X265AMD_DEPTH - 8);
+                    int dqp = qp - R.c->refQP(x, y);
+                    dqp = (dqp + 78 + bd + (bd / 2)) % (52 + bd) - 26 - (bd / 2);
+                    nj.reserved[0] = 1; nj.reserved[1] = (uint8_t)(int8_t)dqp;
+                }
+                /* the neighbour modes inside the block are the chain's: left of units 0 / 2 = units 1 / 3 of the CU to the left, above of units 0 / 1 = units 2 / 3 of the CU above */
+                nj.mode_src[0] = (i & 1) ? (uint8_t)(((i - 1) << 2) | 1) : 0xFF; nj.mode_src[1] = (i & 1) ? (uint8_t)(((i - 1) << 2) | 3) : 0xFF;
+                nj.mode_src[2] = (i & 2) ? (uint8_t)(((i - 2) << 2) | 2) : 0xFF; nj.mode_src[3] = (i & 2) ? (uint8_t)(((i - 2) << 2) | 3) : 0xFF;
+                if (role == 1)
+                {
+                    nj.peer_recon[0] = tiles2[1];
+                    nj.win_dst[0] = split_recon + ((size_t)(8 * (i >> 1)) * 64 + 8 * (i & 1)) * isz;
+                    for (int pl = 0; pl < 2; pl++)
+                    {
+                        nj.peer_recon[1 + pl] = tiles2[1] + (4096 + (size_t)pl * 1024) * isz;
+                        nj.win_dst[1 + pl] = split_recon + (4096 + (size_t)pl * 1024 + (size_t)(4 * (i >> 1)) * 32 + 4 * (i & 1)) * isz;
+                    }
+                }
+                { XA_HOSTPROF("quad8 record push"); memcpy(&jobs[2 * i + (role - 1)], &nj, sizeof(nj)); }
             }
-            { XA_HOSTPROF("quad8 record push"); memcpy(&jobs[2 * i + (role - 1)], &nj, sizeof(nj)); }
+            u0.part_size = keepPart;
+            outs[i].status = 0;
         }
-        u0.part_size = keepPart;
-        outs[i].status = 0;
     }
-    x265amd_cabac_close(coder);
     R.c = nullptr;
     /* what this queue has written is out before the other workgroup looks (a signalling command releases), and that one looks (acquire) */
     int rc = X265AMD_OK;
@@ -1468,17 +1459,29 @@ void xa_intra_ws_free(void* ws)
     }
     delete ip;
 }
+/* The two entries that only start a command bind the CU like an ordinary call (the same allocations and, under RDOQ, the same fill of the estimate table), start it,
+ * and leave the units as they were.  1: started, 0: not possible here, < 0: error. */
+static int intra_start(const IntraCall& a, void** ws, int (IntraRd::*start)())
+{
+    int rc = a.refuse(false, 0);
+    if (rc != X265AMD_OK) return rc;
+    xa_phase(XA_PH_ANALYZER);
+    WsRef w(ws);
+    CuScope scope;
+    rc = w.ip->bind(a, 0, false, scope);
+    return rc != X265AMD_OK ? rc : (w.ip->*start)();
+}
 int xa_check_intra_begin_ws(void* stream, const x265amd_slice_info* si, const x265amd_rd_params* rp, x265amd_cu_unit* units, const uint64_t* h_src, const uint64_t* h_rec,
                             intptr_t stride, intptr_t cstride, const x265amd_rd_cu* cu, uint64_t d_pred, uint64_t d_recon, void** ws)
 {
     if (!ws || !xa_queue_helper(stream) || !xa_queue_helper(xa_queue_helper(stream))) return 0;
-    return intra_cu_impl(2, 0, stream, si, rp, units, h_src, h_rec, stride, cstride, cu, nullptr, d_pred, d_recon, nullptr, nullptr, nullptr, ws);
+    return intra_start({ stream, si, rp, units, h_src, h_rec, stride, cstride, cu, d_pred, d_recon }, ws, &IntraRd::startLargeAhead);
 }
 int xa_intra_in_inter_begin_ws(void* stream, const x265amd_slice_info* si, const x265amd_rd_params* rp, x265amd_cu_unit* units, const uint64_t* h_src, const uint64_t* h_rec,
                                intptr_t stride, intptr_t cstride, const x265amd_rd_cu* cu, uint64_t d_pred, uint64_t d_recon, void** ws)
 {
     if (!ws || !xa_is_queue(stream)) return 0;
-    return intra_cu_impl(3, 0, stream, si, rp, units, h_src, h_rec, stride, cstride, cu, nullptr, d_pred, d_recon, nullptr, nullptr, nullptr, ws);
+    return intra_start({ stream, si, rp, units, h_src, h_rec, stride, cstride, cu, d_pred, d_recon }, ws, &IntraRd::startTryAhead);
 }
 void xa_intra_ws_hint_nxn(void** ws, uint64_t d_pred_nxn, uint64_t d_recon_nxn)
 {
@@ -1487,29 +1490,18 @@ void xa_intra_ws_hint_nxn(void** ws, uint64_t d_pred_nxn, uint64_t d_recon_nxn)
     IntraRd* ip = static_cast<IntraRd*>(*ws);
     ip->hintPred = d_pred_nxn; ip->hintRecon = d_recon_nxn;
 }
-int xa_check_intra_ws(void* stream, const x265amd_slice_info* si, const x265amd_rd_params* rp, x265amd_cu_unit* units, const uint64_t* h_src, const uint64_t* h_rec,
-                      intptr_t stride, intptr_t cstride, const x265amd_rd_cu* cu, int part_size, x265amd_cu_unit* cu_units, uint64_t d_pred, uint64_t d_recon,
-                      x265amd_rd_result* out, int16_t* coeff_out, void** ws)
-{
-    return intra_cu_impl(1, part_size, stream, si, rp, units, h_src, h_rec, stride, cstride, cu, cu_units, d_pred, d_recon, out, coeff_out, nullptr, ws);
-}
-int xa_intra_in_inter_ws(void* stream, const x265amd_slice_info* si, const x265amd_rd_params* rp, x265amd_cu_unit* units, const uint64_t* h_src, const uint64_t* h_rec,
-                         intptr_t stride, intptr_t cstride, const x265amd_rd_cu* cu, x265amd_cu_unit* cu_units, uint64_t d_pred, uint64_t d_recon, x265amd_rd_result* out,
-                         int16_t* coeff_out, uint64_t* info, void** ws)
-{
-    return intra_cu_impl(0, 0, stream, si, rp, units, h_src, h_rec, stride, cstride, cu, cu_units, d_pred, d_recon, out, coeff_out, info, ws);
-}
 
+/* the plain entries keep no working set: one is made and deleted per call, and the call returns with everything done */
 extern "C" int x265amd_intra_in_inter(void* stream, const x265amd_slice_info* si, const x265amd_rd_params* rp, x265amd_cu_unit* units,
                                       const uint64_t* h_src, const uint64_t* h_rec, intptr_t stride, intptr_t cstride, const x265amd_rd_cu* cu,
                                       x265amd_cu_unit* cu_units, uint64_t d_pred, uint64_t d_recon, x265amd_rd_result* out, int16_t* coeff_out, uint64_t* info)
 {
-    return intra_cu_impl(0, 0, stream, si, rp, units, h_src, h_rec, stride, cstride, cu, cu_units, d_pred, d_recon, out, coeff_out, info);
+    return xa_intra_in_inter_ws(stream, si, rp, units, h_src, h_rec, stride, cstride, cu, cu_units, d_pred, d_recon, out, coeff_out, info, nullptr);
 }
 
 extern "C" int x265amd_check_intra(void* stream, const x265amd_slice_info* si, const x265amd_rd_params* rp, x265amd_cu_unit* units,
                                    const uint64_t* h_src, const uint64_t* h_rec, intptr_t stride, intptr_t cstride, const x265amd_rd_cu* cu, int part_size,
                                    x265amd_cu_unit* cu_units, uint64_t d_pred, uint64_t d_recon, x265amd_rd_result* out, int16_t* coeff_out)
 {
-    return intra_cu_impl(1, part_size, stream, si, rp, units, h_src, h_rec, stride, cstride, cu, cu_units, d_pred, d_recon, out, coeff_out, nullptr);
+    return xa_check_intra_ws(stream, si, rp, units, h_src, h_rec, stride, cstride, cu, part_size, cu_units, d_pred, d_recon, out, coeff_out, nullptr);
 }

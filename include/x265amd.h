@@ -875,7 +875,7 @@ int x265amd_pred_inter_search_ex(x265amd_me_ctx* me, void* stream, const x265amd
  * The transform chains of every node of every CU's residual quad-tree run as one x265amd_tu_chain launch (plain quantisation does not
  * depend on the entropy state); the bit counting and the decisions walk the tree on the host in the reference's order with the
  * bit-counting CABAC coder; a second launch assembles the chosen residual, reconstructs and measures the CU.
- * Supported: 4:2:0, rdoqLevel 0-2 (psy-rdoq), no transform skip / lossless / limit-tu / ssim-rd, chroma QP offsets 0. */
+ * Supported: 4:2:0, rdoqLevel 0-2 (psy-rdoq), limit-tu 0 / 2 / 3 / 4, no transform skip / lossless / ssim-rd, chroma QP offsets 0. */
 typedef struct x265amd_rd_params
 {
     double psy_rd;                  /* param.psyRd (RDCost::setPsyRdScale, rdcost.h:43) */

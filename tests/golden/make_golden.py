@@ -46,6 +46,7 @@ def main():
     make_intra_tu_golden()
     make_inter_search_golden()
     make_inter_rd_golden()
+    make_inter_rd_rdoq_golden()
     make_ctu_analysis_golden()
     make_intra_rd_golden()
     make_frame_pipeline_golden()
@@ -232,6 +233,21 @@ def make_inter_rd_golden():
                 out["%d/%d/%s" % (k, i, name)] = a
     np.savez_compressed(os.path.join(T.GOLDEN_DIR, "skip_rd_golden.npz"), **out)
     print("wrote skip_rd_golden.npz with", len(out), "arrays")
+
+
+def make_inter_rd_rdoq_golden():
+    """the same with RDOQ (rdoqLevel 1 / 2, psy-rdoq): the cases of tests/test_inter_rd_rdoq.py -> tests/golden/inter_rd_rdoq_golden.npz"""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("tirq", os.path.join(os.path.dirname(T.GOLDEN_DIR), "test_inter_rd_rdoq.py"))
+    tirq = importlib.util.module_from_spec(spec); spec.loader.exec_module(tirq)
+    out = {}
+    for k, case in enumerate(tirq.CASES):
+        c = tirq.rdoq_case(*case)
+        for i, d in enumerate(T.rd_pack(T.rd_run_ref(T.load_ref(case[0]), c), c)):
+            for name, a in d.items():
+                out["%d/%d/%s" % (k, i, name)] = a
+    np.savez_compressed(os.path.join(T.GOLDEN_DIR, "inter_rd_rdoq_golden.npz"), **out)
+    print("wrote inter_rd_rdoq_golden.npz with", len(out), "arrays")
 
 
 def make_ctu_analysis_golden():
@@ -800,6 +816,9 @@ if __name__ == "__main__":
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "rcrecords":
         make_ratecontrol_golden()
+        sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "rdoq":
+        make_inter_rd_rdoq_golden()
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "fade":
         make_encoder_fade_golden()

@@ -2232,7 +2232,7 @@ def inter_search_run_hip(L, me, c):
 
 
 # ---- residual RD of inter CUs (x265amd_inter_residual_rd vs Search::encodeResAndCalcRdInterCU) ----
-RD_PARAMS_DT = np.dtype([("psy_rd", "<f8"), ("rd_level", "<i4"), ("strong", "<i4"), ("rdoq_level", "<i4"), ("psy_rdoq_scale", "<i4"), ("fast_intra", "<i4"), ("reserved", "<i4")])
+RD_PARAMS_DT = np.dtype([("psy_rd", "<f8"), ("rd_level", "<i4"), ("strong", "<i4"), ("rdoq_level", "<i4"), ("psy_rdoq_scale", "<i4"), ("fast_intra", "<i4"), ("limit_tu", "<i4")])
 RD_RESULT_DT = np.dtype([("rd_cost", "<u8"), ("distortion", "<u8"), ("frac_bits", "<u8"), ("total_bits", "<u4"), ("mv_bits", "<u4"), ("coeff_bits", "<u4"),
                          ("psy_energy", "<u4"), ("luma_distortion", "<u4"), ("chroma_distortion", "<u4"), ("res_energy", "<u4"), ("reserved", "<u4"),
                          ("ctx", "u1", 160)])

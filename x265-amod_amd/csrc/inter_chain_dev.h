@@ -438,7 +438,7 @@ XA_DEV int chain_ref_qp(const ChainLds& S, int k)
 
 /* encodeResAndCalcRdSkipCU and encodeResAndCalcRdInterCU (search.cpp:2770-2975) of the chosen merge candidate of a CU with one transform unit per plane (8x8 ..
  * 32x32: the residual quad-tree is its root), from the units' results S.tr[] and levels, and the choice between them as checkMerge2Nx2N_rd0_4 makes it
- * (analysis.cpp:2852-2880: the residual mode only when strictly cheaper).  Host form: x265amd_skip_rd_host, inter_rd_walk_impl, x265amd_inter_rd_finish (inter_rd.hip).
+ * (analysis.cpp:2852-2880: the residual mode only when strictly cheaper).  Host form: x265amd_skip_rd_host, walk_cu, x265amd_inter_rd_finish (inter_rd.hip).
  * One wavefront; leaves S.skipWins and, in S.ctxS / S.fracS, the skip mode's coder state. */
 XA_DEV void chain_merge_rd(ChainLds& S, int x, int y, int log2, int best, int lane)
 {

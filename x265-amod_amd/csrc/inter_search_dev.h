@@ -116,7 +116,7 @@ template<class JOB> XA_DEV uint64_t search_cost(const JOB& J, chain_sse_t dist, 
     return J.psy_rd ? (uint64_t)dist + ((J.lambda * J.psy_rd * energy) >> 24) + (((uint64_t)bits * J.lambda2) >> 8) : (uint64_t)dist + (((uint64_t)bits * J.lambda2 + 128) >> 8);
 }
 
-/* Search::encodeResAndCalcRdInterCU of the searched 2Nx2N mode (one transform unit per plane; host form: inter_rd_walk_impl + x265amd_inter_rd_finish, inter_rd.hip).
+/* Search::encodeResAndCalcRdInterCU of the searched 2Nx2N mode (one transform unit per plane; host form: walk_cu + x265amd_inter_rd_finish, inter_rd.hip).
  * One wavefront; leaves the result in S.rd*, S.ctxD, S.fracD. */
 XA_DEV void search_inter_rd(SearchLds& S, int log2, int lane)
 {

@@ -62,26 +62,6 @@ struct IntraCall
     }
 };
 
-/* The bit-counting coder of one call and the CU's units as the caller had them: the units go back and the coder is closed on every way out. */
-struct CuScope
-{
-    x265amd_cabac* coder = nullptr;
-    x265amd_cu_unit* first = nullptr; int w4 = 0, u4 = 0;          /* the CU's first unit in the picture's map, the map's row length, the CU's extent in units */
-    std::vector<x265amd_cu_unit> saved;
-    x265amd_cu_unit* row(int yy) const { return first + (size_t)yy * w4; }
-    void save(x265amd_cu_unit* first_, int w4_, int u4_)
-    {
-        first = first_; w4 = w4_; u4 = u4_;
-        saved.resize((size_t)u4 * u4);
-        for (int yy = 0; yy < u4; yy++) memcpy(&saved[(size_t)yy * u4], row(yy), sizeof(x265amd_cu_unit) * u4);
-    }
-    ~CuScope()
-    {
-        for (int yy = 0; yy < u4; yy++) memcpy(row(yy), &saved[(size_t)yy * u4], sizeof(x265amd_cu_unit) * u4);
-        if (coder) x265amd_cabac_close(coder);
-    }
-};
-
 struct IntraRd : RdCost
 {
     hipStream_t st;
@@ -997,9 +977,9 @@ struct IntraRd : RdCost
     }
     bool openCoder(CuScope& scope)
     {
-        c = scope.coder = x265amd_cabac_open(si, units, 1);
-        if (c) c->ctuInProgress = true;          /* the analysis of a CTU asks (cabac_coder.h: lastQP) */
-        return c != nullptr;
+        const bool ok = scope.open(si, units);
+        c = scope.coder;
+        return ok;
     }
     bool allocMain()
     {

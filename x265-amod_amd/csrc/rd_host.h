@@ -1,11 +1,13 @@
 /* The rate-distortion helpers the CU orchestrators share (ctu_analysis.hip, intra_rd.hip, inter_rd.hip): the reference's cost types and arithmetic, the entropy
- * coder's snapshots, the quantiser's QPs and the pooled buffers.  Host code only; every including file gets its own copy (anonymous namespace). */
+ * coder's snapshots, the quantiser's QPs, the pooled buffers and the scope that lends a CU's place in the picture's unit map to a candidate (CuScope: intra_rd.hip,
+ * inter_rd.hip).  Host code only; every including file gets its own copy (anonymous namespace). */
 #ifndef X265AMD_RD_HOST_H
 #define X265AMD_RD_HOST_H
 
 #include "x265amd_host.h"
 #include "../host/cabac_coder.h"
 #include <string.h>
+#include <vector>
 
 namespace {
 
@@ -29,6 +31,45 @@ struct DevBuf
     hipError_t alloc(size_t bytes) { return xa_scratch_alloc(&p, bytes ? bytes : 16); }
 };
 struct MappedBuf : XaMapped { void free() { xa_mapped_free(p); p = nullptr; } };
+
+/* The bit-counting coder of one call, or a CU's units as the caller had them, or both: the units go back and the coder is closed on every way out. */
+struct CuScope
+{
+    x265amd_cabac* coder = nullptr;
+    x265amd_cu_unit* first = nullptr; int w4 = 0, u4 = 0;          /* the CU's first unit in the picture's map, the map's row length, the CU's extent in units */
+    x265amd_cu_unit* candidate = nullptr;                          /* put(): where the map's version of the CU goes before the saved units return */
+    std::vector<x265amd_cu_unit> saved;
+    x265amd_cu_unit* row(int yy) const { return first + (size_t)yy * w4; }
+    /* the coder the analysis of a CTU counts bits with; false: the slice description does not make one */
+    bool open(const x265amd_slice_info* si, x265amd_cu_unit* units)
+    {
+        coder = x265amd_cabac_open(si, units, 1);
+        if (coder) coder->ctuInProgress = true;          /* the analysis of a CTU asks (cabac_coder.h: lastQP) */
+        return coder != nullptr;
+    }
+    void save(x265amd_cu_unit* first_, int w4_, int u4_)
+    {
+        first = first_; w4 = w4_; u4 = u4_;
+        saved.resize((size_t)u4 * u4);
+        for (int yy = 0; yy < u4; yy++) memcpy(&saved[(size_t)yy * u4], row(yy), sizeof(x265amd_cu_unit) * u4);
+    }
+    /* save(), then a candidate's own units (raster, row length u4) take the CU's place in the map */
+    void put(x265amd_cu_unit* first_, int w4_, int u4_, x265amd_cu_unit* cu_units)
+    {
+        save(first_, w4_, u4_);
+        candidate = cu_units;
+        for (int yy = 0; yy < u4; yy++) memcpy(row(yy), candidate + (size_t)yy * u4, sizeof(x265amd_cu_unit) * u4);
+    }
+    ~CuScope()
+    {
+        for (int yy = 0; yy < u4; yy++)
+        {
+            if (candidate) memcpy(candidate + (size_t)yy * u4, row(yy), sizeof(x265amd_cu_unit) * u4);
+            memcpy(row(yy), &saved[(size_t)yy * u4], sizeof(x265amd_cu_unit) * u4);
+        }
+        if (coder) x265amd_cabac_close(coder);
+    }
+};
 
 inline uint32_t zUnit(int ux, int uy)           /* z-order of the 4x4 unit (ux, uy) inside its CTU */
 {

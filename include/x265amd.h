@@ -108,6 +108,11 @@ int x265amd_count_nonzero(int cu, const int16_t* quantCoeff);
 
 /* dct_t / idct_t (primitives.h:153-154) -- cu[cu].dct/idct, dst4x4, idst4x4 */
 void x265amd_dct(int cu, const int16_t* src, int16_t* dst, intptr_t srcStride);
+/* cu[].lowpass_dct (lowpassdct.cpp:34-112), cu 1, 2, 3 (8x8, 16x16, 32x32): the 2x2 cells of the block averaged (`>> 2` of an int16_t sum), the standard transform of
+ * half the size over them, its coefficients in the top-left quadrant of a zero block, and the first coefficient replaced by the sum of all samples -- `<< 1` of a 16-bit
+ * total for 8x8, `>> 1` for 16x16, `>> 3` for 32x32, cut to 16 bits (it wraps).  The reference makes the 16x16 and 32x32 forms active under --lowpass-dct
+ * (primitives.cpp:72-86) and never the 8x8 one.  x265amd_setup_primitives does NOT install the slot CU_lowpass_dct: the installed set is pinned at 943 slots. */
+void x265amd_lowpass_dct(int cu, const int16_t* src, int16_t* dst, intptr_t srcStride);
 void x265amd_idct(int cu, const int16_t* src, int16_t* dst, intptr_t dstStride);
 void x265amd_dst4x4(const int16_t* src, int16_t* dst, intptr_t srcStride);
 void x265amd_idst4x4(const int16_t* src, int16_t* dst, intptr_t dstStride);
@@ -181,6 +186,9 @@ enum x265amd_op
     X265AMD_OP_IP_HPP = 128, X265AMD_OP_IP_HPS, X265AMD_OP_IP_VPP, X265AMD_OP_IP_VPS, X265AMD_OP_IP_VSP, X265AMD_OP_IP_VSS,
     X265AMD_OP_IP_HVPP, X265AMD_OP_IP_P2S
 };
+/* family 2, beside the enumeration (which lists the ops behind installed table slots): cu[size].lowpass_dct, size 1..3; a = source (int16, stride sa), d = N * N
+ * coefficients (x265amd_lowpass_dct above).  A job of another size writes nothing. */
+#define X265AMD_OP_LOWPASS_DCT 80
 
 typedef struct x265amd_job
 {
@@ -278,8 +286,12 @@ typedef struct x265amd_tu_job
     uint64_t resi;                  /* out: N x N reconstructed residual (int16), resi_stride */
     uint64_t recon;                 /* out: N x N reconstruction (pixels), recon_stride */
     int32_t fenc_stride, pred_stride, resi_stride, recon_stride;
-    uint8_t log2_tr_size, ttype, intra, dir_mode, slice_type, qp_scaled, sign_hide, reserved;
+    uint8_t log2_tr_size, ttype, intra, dir_mode, slice_type, qp_scaled, sign_hide;
+    uint8_t flags;                  /* X265AMD_TU_*; 0: the transform of the unit's size.  The other bits are reserved (0) */
 } x265amd_tu_job;
+/* x265amd_tu_job.flags: --lowpass-dct (param.bLowPassDct).  The forward transform of a 16x16 or 32x32 unit -- and of its source block under psy-RDOQ -- is the
+ * low-pass approximation of x265amd_lowpass_dct below; smaller units and every inverse transform are not touched.  Per job: two encoders of one process may differ. */
+#define X265AMD_TU_LOWPASS 1
 
 typedef struct x265amd_tu_result
 {
@@ -763,13 +775,16 @@ typedef struct x265amd_slice_info
     int32_t num_ref_idx[2];
     int32_t max_num_merge_cand;
     int32_t use_dqp, max_cu_dqp_depth;      /* pps.bUseDQP, pps.maxCuDQPDepth */
-    int32_t sign_hide, tq_bypass_enabled;   /* pps.bSignHideEnabled, pps.bTransquantBypassEnabled */
+    int32_t sign_hide, tq_bypass_enabled;   /* pps.bSignHideEnabled (bit 0, X265AMD_SLICE_SIGN_HIDE; bit 8, X265AMD_SLICE_LOWPASS_DCT: param.bLowPassDct -- every transform
+                                             * unit made for the slice carries X265AMD_TU_LOWPASS), pps.bTransquantBypassEnabled */
     int32_t wpp;                            /* pps.bEntropyCodingSyncEnabled (only read by the last-coded-QP rule) */
     int32_t max_cu_depth;                   /* param.maxCUDepth: log2(maxCUSize) - log2(minCUSize) */
     int32_t max_amp_depth;                  /* sps.maxAMPDepth */
     int32_t tu_log2_min, tu_log2_max;       /* sps.quadtreeTULog2MinSize / MaxSize */
     int32_t tu_max_depth_inter, tu_max_depth_intra;
 } x265amd_slice_info;
+#define X265AMD_SLICE_SIGN_HIDE 1
+#define X265AMD_SLICE_LOWPASS_DCT 0x100
 typedef struct x265amd_cabac x265amd_cabac;
 /* units: the picture's map (kept by reference; its qp fields are updated).  bits_only != 0: no bitstream, fractional bits are
  * counted instead (the reference's m_fracBits, FIX15).  Contexts start at Entropy::resetEntropy(slice). */

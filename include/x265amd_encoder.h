@@ -190,6 +190,17 @@ typedef struct x265amd_param_ext {
     int32_t reserved[12];       /* zero */
 } x265amd_param_ext;
 x265amd_encoder* x265amd_encoder_open_ext(const x265amd_param* p, const x265amd_param_ext* ext);   /* ext == NULL: x265amd_encoder_open(p) */
+/* A second record of the same manners (x265amd_param_ext is pinned at its size and its reserved words are refused when set): a record cut short of a member reads that
+ * member as zero, non-zero reserved words and sizes that are no multiple of 4 or above sizeof(x265amd_param_tools) are refused by name.
+ *   bLowPassDct (--lowpass-dct; primitives.cpp:72-86, :278-281, lowpassdct.cpp:64-112): the forward transform of every 16x16 and 32x32 unit (luma, and the 16x16 chroma units) is
+ *     the low-pass approximation x265amd_lowpass_dct; under psy-RDOQ the source block's transform is too.  Inverse transforms and smaller units are untouched.  Not with
+ *     shardCount > 1.  The info SEI's text ends in " lowpass-dct=1" when it is on. */
+typedef struct x265amd_param_tools {
+    uint32_t size;              /* sizeof(x265amd_param_tools) as the caller knows it; fields beyond it read as 0 */
+    int32_t bLowPassDct;        /* param.bLowPassDct (--lowpass-dct; 0) */
+    int32_t reserved[14];       /* zero */
+} x265amd_param_tools;
+x265amd_encoder* x265amd_encoder_open_tools(const x265amd_param* p, const x265amd_param_ext* ext, const x265amd_param_tools* tools);   /* tools == NULL: x265amd_encoder_open_ext(p, ext) */
 /* VPS, SPS, PPS; the array and payloads stay valid until the next call on this encoder.  Returns the total payload size or -1. */
 int x265amd_encoder_headers(x265amd_encoder* enc, x265amd_nal** pp_nal, uint32_t* pi_nal);
 /* pic_in == NULL flushes.  Returns 1 when a coded picture was emitted (its NAL units in *pp_nal, its reconstruction copied to

@@ -8,7 +8,7 @@
  *             --crf F --qp N --aq-mode N --aq-strength F --[no-]cutree --qcomp F --qg-size N --bframes N --b-adapt N --[no-]b-pyramid --[no-]open-gop --keyint N --min-keyint N
  *             --scenecut N --no-scenecut --[no-]hist-scenecut --rc-lookahead N --lookahead-slices N --ref N --limit-refs N --rd N --rdoq-level N --psy-rd F --psy-rdoq F --me name --subme N
  *             --merange N --max-merge N --[no-]rect --[no-]amp --[no-]limit-modes --[no-]early-skip --rskip N (0, 1, 2) --rskip-edge-threshold N --[no-]weightp --[no-]weightb --[no-]sao --[no-]sao-non-deblock --[no-]limit-sao
- *             --selective-sao N (0..4) --[no-]deblock --[no-]wpp
+ *             --selective-sao N (0..4) --lowpass-dct --[no-]deblock --[no-]wpp
  *             --tu-intra-depth N --tu-inter-depth N --[no-]signhide --[no-]strong-intra-smoothing --[no-]temporal-mvp --[no-]b-intra --[no-]fast-intra --[no-]info --[no-]psnr --[no-]ssim --max-cll C,F
  *             --frame-threads N --pools S --min-luma N --max-luma N ...] [-D|--output-depth 8|10] [--dither]
  *
@@ -173,6 +173,8 @@ int main(int argc, char** argv)
     for (auto& o : opts)
     {
         const char* name = o.first.c_str() + 2;
+        /* (the reference's option table has --lowpass-dct and no --no-lowpass-dct, x265cli.h:341; x265_param_parse would take the name) */
+        if (!strcmp(name, "no-lowpass-dct")) { fprintf(stderr, "x265amd: unknown option %s\n", o.first.c_str()); return 2; }
         /* the argument behind an option, if there is one, is its value; an option that stands alone is a switch (x265_param_parse takes NULL as "true") */
         const int r = api.param_parse(p, name, o.second);
         if (r == -1) { fprintf(stderr, "x265amd: unknown option %s\n", o.first.c_str()); return 2; }

@@ -335,7 +335,7 @@ struct Analyzer : RdCost
          * twelve units' chains take on the device what the host's two round trips took, and the pictures' links are the last column's searched CTUs either way -- so it
          * stays off unless asked for (X265AMD_CHAIN_64=1); the host's merge check goes on from the device's candidate instead (chainMergeFrom) */
         { static const bool on64 = xa_env_nonzero("X265AMD_CHAIN_64"); J.chain64_off = !on64; }
-        J.rd_level = A->rd_level; J.sign_hide = si->sign_hide != 0; J.max_cu_depth = si->max_cu_depth;
+        J.rd_level = A->rd_level; J.sign_hide = si->sign_hide & X265AMD_SLICE_SIGN_HIDE; J.tu_flags = (si->sign_hide & X265AMD_SLICE_LOWPASS_DCT) ? X265AMD_TU_LOWPASS : 0; J.max_cu_depth = si->max_cu_depth;
         if (!chain.dScratch.p && chain.dScratch.alloc(x265amd_inter_rd_scratch_bytes()) != hipSuccess) return fail("chain scratch");
         J.scratch = (uint64_t)(uintptr_t)chain.dScratch.p;
         J.frac = md[depth].cur.frac; memcpy(J.ctx, md[depth].cur.ctx, X265AMD_CTX_STRIDE);
@@ -1066,7 +1066,7 @@ struct Analyzer : RdCost
         J.pred_tile = tileAddr(predTile(depth, PRED_2Nx2N)); J.recon_tile = tileAddr(reconTile(depth, PRED_2Nx2N));
         J.lambda = lambda; J.lambda2 = lambda2; J.psy_rd = psyRd;
         quantQps(qp, J.qp_luma, J.qp_chroma);
-        J.sign_hide = si->sign_hide != 0; J.chroma_sa8d = A->rd_level >= 3; J.rd_level = A->rd_level; J.do_rd = 1; J.slice_type = si->slice_type;
+        J.sign_hide = si->sign_hide & X265AMD_SLICE_SIGN_HIDE; J.tu_flags = (si->sign_hide & X265AMD_SLICE_LOWPASS_DCT) ? X265AMD_TU_LOWPASS : 0; J.reserved2 = 0; J.chroma_sa8d = A->rd_level >= 3; J.rd_level = A->rd_level; J.do_rd = 1; J.slice_type = si->slice_type;
         {
             const x265amd_cu_unit* l = (x >> 2) > 0 ? &units[(y >> 2) * w4 + (x >> 2) - 1] : nullptr;
             const x265amd_cu_unit* a = (y >> 2) > 0 ? &units[((y >> 2) - 1) * w4 + (x >> 2)] : nullptr;

@@ -79,9 +79,20 @@ void x265amd_encoder::fillStreamParams(x265amd_stream_params& s) const
 
 extern "C" x265amd_encoder* x265amd_encoder_open(const x265amd_param* p) { return x265amd_encoder_open_ext(p, nullptr); }
 
-extern "C" x265amd_encoder* x265amd_encoder_open_ext(const x265amd_param* p, const x265amd_param_ext* extIn)
+extern "C" x265amd_encoder* x265amd_encoder_open_ext(const x265amd_param* p, const x265amd_param_ext* extIn) { return x265amd_encoder_open_tools(p, extIn, nullptr); }
+
+extern "C" x265amd_encoder* x265amd_encoder_open_tools(const x265amd_param* p, const x265amd_param_ext* extIn, const x265amd_param_tools* toolsIn)
 {
     if (!p) { xa_fail(X265AMD_EINVAL, "encoder_open: null param"); return nullptr; }
+    /* the second record, of the same manners as the first */
+    x265amd_param_tools tools;
+    memset(&tools, 0, sizeof(tools));
+    if (toolsIn)
+    {
+        if (toolsIn->size < sizeof(uint32_t) || (toolsIn->size & 3) || toolsIn->size > sizeof(tools)) { xa_fail(X265AMD_EINVAL, "encoder_open: x265amd_param_tools.size (a multiple of 4 up to sizeof(x265amd_param_tools))"); return nullptr; }
+        memcpy(&tools, toolsIn, toolsIn->size);
+        for (int32_t r : tools.reserved) if (r) { xa_fail(X265AMD_EINVAL, "encoder_open: x265amd_param_tools.reserved must be zero"); return nullptr; }
+    }
     /* the extension record as far as the caller knows it: what lies beyond its size reads as zero; a record longer than this library's could name options it does not know */
     x265amd_param_ext ext;
     memset(&ext, 0, sizeof(ext));
@@ -174,6 +185,8 @@ extern "C" x265amd_encoder* x265amd_encoder_open_ext(const x265amd_param* p, con
         /* the SAO options: the pre-deblock record and the per-picture switch are the coding object's own; no test runs several ranks */
         XA_REQUIRE(!(ext.bSaoNonDeblocked || ext.bLimitSAO || (ext.selectiveSAO && ext.selectiveSAO != 4)) || p->shardCount <= 1,
                    "bSaoNonDeblocked / bLimitSAO / selectiveSAO with pictures coded on several GPUs (shardCount > 1) is not built");
+        /* the low-pass transform: the flag rides in the coding object's slice record; no test runs several ranks */
+        XA_REQUIRE(!tools.bLowPassDct || p->shardCount <= 1, "bLowPassDct with pictures coded on several GPUs (shardCount > 1) is not built");
         XA_REQUIRE(p->limitReferences >= 0 && p->limitReferences <= 3, "limitReferences outside 0..3");
         XA_REQUIRE(!p->bEnableAMP || p->bEnableRectInter, "bEnableAMP needs bEnableRectInter");
 #undef XA_REQUIRE
@@ -183,6 +196,7 @@ extern "C" x265amd_encoder* x265amd_encoder_open_ext(const x265amd_param* p, con
     std::unique_ptr<x265amd_encoder> e(new x265amd_encoder);
     e->p = *p;
     e->selectiveSAO = ext.selectiveSAO; e->limitSAO = ext.bLimitSAO != 0; e->saoNonDeblock = ext.bSaoNonDeblocked != 0;
+    e->lowPassDct = tools.bLowPassDct != 0;
     /* a size that is no multiple of the smallest CU is coded padded to one, the pad replicating the last column / row, and the SPS's conformance window takes it off again
      * (Encoder::configure, encoder.cpp:4081-4090, :4300-4308; PicYuv::copyFromPicture) */
     e->srcW = p->sourceWidth; e->srcH = p->sourceHeight;
@@ -346,6 +360,7 @@ extern "C" x265amd_encoder* x265amd_encoder_open_ext(const x265amd_param* p, con
                  p->bEnableEarlySkip != 0, p->recursionSkipMode, p->bEnableWeightedPred != 0, p->bEnableWeightedBiPred != 0, p->bEnableSAO != 0, p->bEnableLoopFilter != 0, p->bEnableWavefront != 0,
                  p->tuQTMaxIntraDepth, p->tuQTMaxInterDepth, p->bEnableSignHiding != 0, p->bEnableStrongIntraSmoothing != 0, p->bEnableTemporalMvp != 0, p->bIntraInBFrames != 0, p->bEnableFastIntra != 0,
                  e->saoNonDeblock, e->selectiveSAO, e->limitSAO);
+        if (e->lowPassDct) strncat(text, " lowpass-dct=1", sizeof(text) - strlen(text) - 1);         /* (only when on: with it off every header byte is as before) */
         uint8_t sei[1400];
         const size_t m = x265amd_write_info_sei(text, sei, sizeof(sei));
         if (!m) { xa_fail(X265AMD_EINVAL, "encoder_open: info SEI"); return nullptr; }

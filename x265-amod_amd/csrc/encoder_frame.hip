@@ -97,7 +97,7 @@ static void frameContext(const x265amd_encoder& e, Pic& pic, FrameCtx& c)
     memset(&si, 0, sizeof(si));
     si.pic_width = e.W; si.pic_height = e.H; si.slice_type = stype; si.slice_qp = pic.sliceQp;
     si.num_ref_idx[0] = info.num_ref_idx[0]; si.num_ref_idx[1] = info.num_ref_idx[1];
-    si.max_num_merge_cand = p.maxNumMergeCand; si.sign_hide = p.bEnableSignHiding != 0; si.wpp = p.bEnableWavefront != 0;
+    si.max_num_merge_cand = p.maxNumMergeCand; si.sign_hide = (p.bEnableSignHiding != 0 ? X265AMD_SLICE_SIGN_HIDE : 0) | (e.lowPassDct ? X265AMD_SLICE_LOWPASS_DCT : 0); si.wpp = p.bEnableWavefront != 0;
     si.use_dqp = e.useDqp; si.max_cu_dqp_depth = e.maxCuDqpDepth;
     si.max_cu_depth = 3; si.max_amp_depth = p.bEnableAMP ? 3 : 0; si.tu_log2_min = 2; si.tu_log2_max = 5;
     si.tu_max_depth_inter = p.tuQTMaxInterDepth; si.tu_max_depth_intra = p.tuQTMaxIntraDepth;

@@ -221,6 +221,7 @@ struct x265amd_encoder
     pixel* uploadBuf = nullptr;         /* pinned: the padded input picture as uploadPicture puts it together (hipHostFree in the destructor) */
     /* x265amd_param_ext as Encoder::configure's rules left it (x265amd_encoder_open_ext): selectiveSAO is 1..4 whenever p.bEnableSAO is set */
     int selectiveSAO = 0; bool limitSAO = false, saoNonDeblock = false;
+    bool lowPassDct = false;            /* x265amd_param_tools.bLowPassDct: every slice record says X265AMD_SLICE_LOWPASS_DCT */
     /* Encoder::encode's choice per picture (encoder.cpp:2343-2364): slice->m_bUseSao.  IS_REFERENCED is fixed by the type, as everywhere here */
     bool picSao(const Pic& pic) const
     {

@@ -75,7 +75,7 @@ struct alignas(8) XaChainJob
     int32_t skip_recon_tile, merge_recon_tile, chain64_off;     /* chain64_off: a CU above the largest transform with a level somewhere goes to the host at once (the default; X265AMD_CHAIN_64=1: chain_merge_rd64) */
     int32_t frame_parallel, search_range, chroma_sa8d, slice_type, qp_luma, qp_chroma, tu_log2_max;
     int32_t guard_on, guard_r0, guard_r1, guard_need;           /* reference rows guard_r0 .. guard_r1 are final up to column guard_need (the picture width: all of them) */
-    int32_t ctu_x, ctu_y, reserved1;
+    int32_t ctu_x, ctu_y, tu_flags;          /* tu_flags: x265amd_tu_job.flags of every transform unit the chain makes (X265AMD_TU_LOWPASS) */
     uint64_t lambda;                        /* RDCost::m_lambda (FIX8) of the CTU's QP: calcRdSADCost, calcPsyRdCost */
     uint64_t lambda2;                       /* RDCost::m_lambda2 */
     uint32_t psy_rd;                        /* RDCost::m_psyRd (0: off) */
@@ -343,7 +343,7 @@ template<int TAPS> XA_DEV int chain_pred_tile(const x265amd_mc_job& j, const McS
 }
 
 /* the residual of one transform unit: does it quantise to nothing?  (Quant::transformNxN without sign-bit hiding: a unit without levels has none to hide) */
-template<class G> XA_DEV uint32_t chain_tu_levels(TuLds& s, const pixel* fenc, int fs, const pixel* pred, int ps, int log2N, int ttype, int sliceType, int qpScaled, const G& g)
+template<class G> XA_DEV uint32_t chain_tu_levels(TuLds& s, const pixel* fenc, int fs, const pixel* pred, int ps, int log2N, int ttype, int sliceType, int qpScaled, int lowpass, const G& g)
 {
     const int N = 1 << log2N;
     for (int i = g.idx; i < N * N; i += g.step())
@@ -352,7 +352,7 @@ template<class G> XA_DEV uint32_t chain_tu_levels(TuLds& s, const pixel* fenc, i
         s.a[i] = (int16_t)((int)fenc[y * fs + x] - (int)pred[y * ps + x]);
     }
     g.sync();
-    return grp_tu_forward(s, log2N, ttype, 0, 0, sliceType, qpScaled, 0, g);
+    return grp_tu_forward(s, log2N, ttype, 0, 0, sliceType, qpScaled, 0, lowpass, g);
 }
 
 
@@ -957,7 +957,7 @@ XA_DEV void block_inter_chain(const XaChainJob* jobAddr, char* smem, int tid)
                 if (lg >= 5)
                 {
                     __syncthreads();
-                    const uint32_t ns = chain_tu_levels(TL[XA_SERVER_WAVES], fenc, fs, pred, ps, lg, tt, J.slice_type, qp, XaBlock{ tid, NT, S.red });
+                    const uint32_t ns = chain_tu_levels(TL[XA_SERVER_WAVES], fenc, fs, pred, ps, lg, tt, J.slice_type, qp, J.tu_flags, XaBlock{ tid, NT, S.red });
                     if (ns && tid == 0) S.anyLevel |= 1 << k;
                     __syncthreads();
                     if (S.anyLevel && !tree) break;
@@ -966,7 +966,7 @@ XA_DEV void block_inter_chain(const XaChainJob* jobAddr, char* smem, int tid)
                 {
                     if ((small % XA_SERVER_WAVES) == wv)
                     {
-                        const uint32_t ns = chain_tu_levels(TL[wv], fenc, fs, pred, ps, lg, tt, J.slice_type, qp, XaWave{ lane });
+                        const uint32_t ns = chain_tu_levels(TL[wv], fenc, fs, pred, ps, lg, tt, J.slice_type, qp, J.tu_flags, XaWave{ lane });
                         if (ns && lane == 0) atomicOr(&S.anyLevel, 1 << k);
                     }
                     small++;
@@ -1025,7 +1025,7 @@ XA_DEV void block_inter_chain(const XaChainJob* jobAddr, char* smem, int tid)
                         j.recon = J.scratch + 6144 * 4 + off * isz;
                         j.fenc_stride = fs; j.pred_stride = ps; j.resi_stride = n; j.recon_stride = n;
                         j.log2_tr_size = (uint8_t)lg; j.ttype = (uint8_t)tt; j.intra = 0; j.dir_mode = 0; j.slice_type = (uint8_t)J.slice_type;
-                        j.qp_scaled = (uint8_t)qp; j.sign_hide = (uint8_t)J.sign_hide;
+                        j.qp_scaled = (uint8_t)qp; j.sign_hide = (uint8_t)J.sign_hide; j.flags = (uint8_t)J.tu_flags;
                     }
                 }
                 __syncthreads();
@@ -1084,7 +1084,7 @@ XA_DEV void block_inter_chain(const XaChainJob* jobAddr, char* smem, int tid)
                 j.recon = J.scratch + 1536 * 4 + off * isz;
                 j.fenc_stride = p ? J.cstride : J.stride; j.pred_stride = p ? 32 : 64; j.resi_stride = n; j.recon_stride = n;
                 j.log2_tr_size = (uint8_t)(p ? C : log2); j.ttype = (uint8_t)p; j.intra = 0; j.dir_mode = 0; j.slice_type = (uint8_t)J.slice_type;
-                j.qp_scaled = (uint8_t)(p ? J.qp_chroma : J.qp_luma); j.sign_hide = (uint8_t)J.sign_hide;
+                j.qp_scaled = (uint8_t)(p ? J.qp_chroma : J.qp_luma); j.sign_hide = (uint8_t)J.sign_hide; j.flags = (uint8_t)J.tu_flags;
             }
             __syncthreads();
             if (log2 == 5)

@@ -115,7 +115,8 @@ static int make_plan(const x265amd_slice_info* si, const x265amd_rd_cu& cu, int 
     int count = firstJob;
     x265amd_tu_job j;
     memset(&j, 0, sizeof(j));
-    j.slice_type = (uint8_t)si->slice_type; j.sign_hide = (uint8_t)(si->sign_hide != 0);
+    j.slice_type = (uint8_t)si->slice_type; j.sign_hide = (uint8_t)(si->sign_hide & X265AMD_SLICE_SIGN_HIDE);
+    j.flags = (uint8_t)((si->sign_hide & X265AMD_SLICE_LOWPASS_DCT) ? X265AMD_TU_LOWPASS : 0);
     for (int L = hi; L >= P.range[0]; L--)
     {
         const int N = 1 << L, nt = P.size >> L;

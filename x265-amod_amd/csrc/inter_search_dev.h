@@ -32,6 +32,7 @@ struct alignas(8) XaSearchJob
     int32_t qp_luma, qp_chroma, sign_hide, chroma_sa8d, rd_level, skip_ctx, do_rd, slice_type;
     int32_t dqp;                            /* delta QP (PPS cu_qp_delta_enabled): bits 0-7 the CU's cu_qp_delta as Entropy::codeDeltaQP wraps it (int8), bit 16 on, bit 17 the CU is a
                                              * quantisation group or above it (Search::checkDQP prices the syntax element a second time); 0: no delta QP */
+    int32_t tu_flags, reserved2;            /* tu_flags: x265amd_tu_job.flags of the CU's transform units (X265AMD_TU_LOWPASS) */
     uint64_t frac;                          /* the coder's state in front of the CU (m_rqt[depth].cur) */
     uint8_t ctx[X265AMD_CTX_STRIDE];
 };
@@ -459,7 +460,7 @@ XA_DEV void block_inter_search(const XaSearchJob* jobAddr, char* smem, int tid)
             j.recon = tuScratch + 1536 * 4 + off * isz;
             j.fenc_stride = p ? J.cstride : J.stride; j.pred_stride = p ? 32 : 64; j.resi_stride = n; j.recon_stride = n;
             j.log2_tr_size = (uint8_t)(p ? C : log2); j.ttype = (uint8_t)p; j.intra = 0; j.dir_mode = 0; j.slice_type = (uint8_t)J.slice_type;
-            j.qp_scaled = (uint8_t)(p ? J.qp_chroma : J.qp_luma); j.sign_hide = (uint8_t)J.sign_hide;
+            j.qp_scaled = (uint8_t)(p ? J.qp_chroma : J.qp_luma); j.sign_hide = (uint8_t)J.sign_hide; j.flags = (uint8_t)J.tu_flags;
         }
         __syncthreads();
         if (log2 == 5)

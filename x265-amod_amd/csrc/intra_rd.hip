@@ -243,7 +243,8 @@ struct IntraRd : RdCost
         j.tu.recon = recon; j.tu.recon_stride = reconStride;
         j.tu.fenc_stride = (int32_t)ps;
         j.tu.log2_tr_size = (uint8_t)log2N; j.tu.ttype = (uint8_t)plane; j.tu.intra = 1; j.tu.dir_mode = (uint8_t)mode;
-        j.tu.slice_type = (uint8_t)si->slice_type; j.tu.qp_scaled = (uint8_t)(plane ? qpChromaScaled : qpLumaScaled); j.tu.sign_hide = (uint8_t)(si->sign_hide != 0);
+        j.tu.slice_type = (uint8_t)si->slice_type; j.tu.qp_scaled = (uint8_t)(plane ? qpChromaScaled : qpLumaScaled); j.tu.sign_hide = (uint8_t)(si->sign_hide & X265AMD_SLICE_SIGN_HIDE);
+        j.tu.flags = (uint8_t)((si->sign_hide & X265AMD_SLICE_LOWPASS_DCT) ? X265AMD_TU_LOWPASS : 0);
         j.nb = rec[plane] + ((uint64_t)(y >> sh) * ps + (x >> sh)) * isz;
         j.nb_stride = (int32_t)ps;
         j.strong_smoothing = (uint8_t)(rp->strong_intra_smoothing != 0);

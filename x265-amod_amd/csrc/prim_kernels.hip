@@ -6,6 +6,7 @@
  */
 #include "x265amd_dev.h"
 #include "x265amd_host.h"
+#include "tu_dev.h"
 
 #define WAVES_PER_BLOCK 4
 
@@ -285,6 +286,17 @@ __global__ __launch_bounds__(256) void k_transform(const x265amd_job* jobs, int 
         wave_fwd_pass(T, log2N, blk, tmp, log2N - 1 + XA_DEPTH - 8, lane);
         xa_wave_sync();
         wave_fwd_pass(T, log2N, tmp, P<int16_t>(j.d), log2N + 6, lane);
+        break;
+    }
+    case X265AMD_OP_LOWPASS_DCT:    /* lowpassdct.cpp:34-112; size 1..3 */
+    {
+        int log2N = j.size + 2, N = 1 << log2N;
+        if (j.size < 1 || j.size > 3) break;
+        const int16_t* s = P<const int16_t>(j.a);
+        for (int i = lane; i < N * N; i += XA_WAVE)
+            blk[i] = s[(i >> log2N) * j.sa + (i & (N - 1))];
+        xa_wave_sync();
+        grp_lowpass_fwd(blk, P<int16_t>(j.d), log2N, tmp, XaWave{ lane });
         break;
     }
     case X265AMD_OP_IDCT:           /* dct.cpp:544-610 */

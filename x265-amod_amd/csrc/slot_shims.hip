@@ -353,6 +353,11 @@ static void inv_tr(int op, int cu, const int16_t* src, int16_t* dst, intptr_t st
     s.run();
 }
 void x265amd_dct(int cu, const int16_t* src, int16_t* dst, intptr_t stride) { fwd_tr(X265AMD_OP_DCT, cu, src, dst, stride); }
+void x265amd_lowpass_dct(int cu, const int16_t* src, int16_t* dst, intptr_t stride)
+{
+    if (cu < 1 || cu > 3) { fprintf(stderr, "x265amd: fatal: x265amd_lowpass_dct: cu %d (8x8, 16x16 and 32x32 have a low-pass form)\n", cu); abort(); }
+    fwd_tr(X265AMD_OP_LOWPASS_DCT, cu, src, dst, stride);
+}
 void x265amd_idct(int cu, const int16_t* src, int16_t* dst, intptr_t stride) { inv_tr(X265AMD_OP_IDCT, cu, src, dst, stride); }
 void x265amd_dst4x4(const int16_t* src, int16_t* dst, intptr_t stride) { fwd_tr(X265AMD_OP_DST4, 0, src, dst, stride); }
 void x265amd_idst4x4(const int16_t* src, int16_t* dst, intptr_t stride) { inv_tr(X265AMD_OP_IDST4, 0, src, dst, stride); }

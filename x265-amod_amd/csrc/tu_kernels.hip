@@ -61,9 +61,9 @@ __global__ __launch_bounds__(64) void k_tu_solo(TuSoloJob j)
         {
             RdoqLds& r = *reinterpret_cast<RdoqLds*>(tu_smem + sizeof(TuLds));
             RdoqParams P = { reinterpret_cast<const int*>(j.est), j.lambda2, j.lambda, j.psyRdoqScale, j.rdoqLevel, j.tuDepth };
-            ns = wave_tu_forward_rdoq(s, r, P, reinterpret_cast<const pixel*>(j.fenc), j.fencStride, j.log2N, j.ttype, j.intra, j.dirMode, j.qpScaled, j.signHide, lane);
+            ns = wave_tu_forward_rdoq(s, r, P, reinterpret_cast<const pixel*>(j.fenc), j.fencStride, j.log2N, j.ttype, j.intra, j.dirMode, j.qpScaled, j.signHide, 0, lane);
         }
-        else ns = wave_tu_forward(s, j.log2N, j.ttype, j.intra, j.dirMode, j.sliceType, j.qpScaled, j.signHide, lane);
+        else ns = wave_tu_forward(s, j.log2N, j.ttype, j.intra, j.dirMode, j.sliceType, j.qpScaled, j.signHide, 0, lane);
         int16_t* coeff = reinterpret_cast<int16_t*>(j.outp);
         for (int i = lane; i < numCoeff; i += XA_WAVE) coeff[i] = s.q[i];
         if (lane == 0) *reinterpret_cast<uint64_t*>(j.numSigOut) = ns;

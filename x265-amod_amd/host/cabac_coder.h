@@ -707,7 +707,7 @@ struct x265amd_cabac
         const int gType = log2N >= 4 ? 0 : scanType;
         const int ncg = 1 << (2 * (log2N - 2));
         const uint32_t log2CG = (uint32_t)log2N - 2, cgStride = (uint32_t)N >> 2;
-        const bool hideSign = si.sign_hide && !u.tq_bypass;
+        const bool hideSign = (si.sign_hide & X265AMD_SLICE_SIGN_HIDE) && !u.tq_bypass;
         int lastSet = -1, lastK = -1;
         uint64_t cgFlags = 0;
         for (int g = ncg - 1; g >= 0 && lastSet < 0; g--)

@@ -206,7 +206,8 @@ int abi_param_parse(void* p, const char* name, const char* value)
         { "hdr", X265ABI_PARAM_bEmitHDR10SEI }, { "cll", X265ABI_PARAM_bEmitCLL }, { "tskip", X265ABI_PARAM_bEnableTransformSkip }, { "lossless", X265ABI_PARAM_bLossless },
         { "hist-scenecut", X265ABI_PARAM_bHistBasedSceneCut },            /* (param.cpp:1279) */
         { "psnr", X265ABI_PARAM_bEnablePsnr }, { "ssim", X265ABI_PARAM_bEnableSsim },
-        { "sao-non-deblock", X265ABI_PARAM_bSaoNonDeblocked }, { "limit-sao", X265ABI_PARAM_bLimitSAO } };            /* (param.cpp:1099, :1310) */
+        { "sao-non-deblock", X265ABI_PARAM_bSaoNonDeblocked }, { "limit-sao", X265ABI_PARAM_bLimitSAO },            /* (param.cpp:1099, :1310) */
+        { "lowpass-dct", X265ABI_PARAM_bLowPassDct } };            /* (param.cpp:1322) */
     if (!strcmp(key, "deblock") && !neg && value)
     {
         /* --deblock tc:beta | tc,beta | tc | a truth value (param.cpp:1083-1097) */
@@ -483,7 +484,12 @@ void* abi_encoder_open(void* p)
     memset(&ext, 0, sizeof(ext));
     ext.size = sizeof(ext);
     ext.bSaoNonDeblocked = PI(p, bSaoNonDeblocked) != 0; ext.bLimitSAO = PI(p, bLimitSAO) != 0; ext.selectiveSAO = PI(p, selectiveSAO);
-    x265amd_encoder* e = x265amd_encoder_open_ext(&q, &ext);
+    /* --lowpass-dct (x265_param.bLowPassDct) */
+    x265amd_param_tools tools;
+    memset(&tools, 0, sizeof(tools));
+    tools.size = sizeof(tools);
+    tools.bLowPassDct = PI(p, bLowPassDct) != 0;
+    x265amd_encoder* e = x265amd_encoder_open_tools(&q, &ext, &tools);
     if (!e) return nullptr;
     AbiEncoder* a = new AbiEncoder;
     a->enc = e; a->width = q.sourceWidth; a->height = q.sourceHeight;

@@ -745,6 +745,22 @@ int x265amd_filter_plan(int width, int height, const int32_t* analysed, int32_t*
 int x265amd_filter_ready(int width, int height, const int32_t* analysed, const int32_t* done_top, const int32_t* done_full,
                          int min_chunk, int min_chunk_last, int early_top);
 
+/* --- which prepared pictures get a frame task now (host code, host/launch_plan.cpp): the start rule of x265amd_encoder_encode.  pics: the pictures that are prepared
+ * and not collected yet, in coding order (the first one is collected next).  type: X265_TYPE_* (1 IDR, 2 I, 3 P, 4 referenced B, 5 b); referenced: later pictures may
+ * reference it; started: it has a task; finished: its task has ended; refs[0 .. num_refs - 1]: its reference pictures as places in the list, -1 for a picture that has
+ * been collected (a reference precedes the picture in coding order).  running: tasks started and not collected; frame_threads: the parameter frameNumThreads (>= 1);
+ * ctu_h: CTU rows of a picture; frame_parallel: pictures are coded side by side.  start (room for num_pics): the places to start now, IN THIS ORDER; ahead (room for
+ * num_pics, or NULL): how each starts, X265AMD_LAUNCH_*.  The first picture always starts; pictures start in coding order while at most frame_threads run; with
+ * frame_parallel an I picture starts when it is typed, and behind a running I picture at the head referenced pictures start ahead of their turn in coding order while at
+ * most frame_threads + ref_cap run, then leaf b pictures while at most frame_threads + leaf_cap run (x265amd_launch_caps: by picture size).  NEVER a picture one of whose
+ * references has neither a task (before the call or earlier in `start`) nor been collected.  Returns X265AMD_OK or X265AMD_EINVAL. */
+enum { X265AMD_LAUNCH_MAX_REFS = 32 };
+enum { X265AMD_LAUNCH_IN_TURN = 0, X265AMD_LAUNCH_INTRA = 1, X265AMD_LAUNCH_AHEAD_REF = 2, X265AMD_LAUNCH_AHEAD_LEAF = 3 };
+typedef struct x265amd_launch_pic { int32_t type, referenced, started, finished, num_refs; int32_t refs[X265AMD_LAUNCH_MAX_REFS]; } x265amd_launch_pic;
+int x265amd_launch_plan(const x265amd_launch_pic* pics, int num_pics, int running, int frame_threads, int ctu_h, int frame_parallel,
+                        int32_t* start, int32_t* ahead, int* num_start);
+int x265amd_launch_caps(int ctu_h, int* ref_cap, int* leaf_cap);
+
 /* --- final entropy coding of CTUs: the CABAC write pass, host code.  Entropy::encodeCTU / encodeCU /
  * encodeTransform / codePredInfo / codeCoeffNxN and the arithmetic coder (reference: source/encoder/entropy.cpp:768-1222, :1431-2200,
  * :2399-2612) with CUData's context derivations (source/common/cudata.cpp:814-1012); 4:2:0, no transform skip.

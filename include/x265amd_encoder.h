@@ -267,7 +267,10 @@ int x265amd_encoder_owns(const x265amd_encoder* enc, uint64_t coding_index);
  * With n >= 31 also what Encoder::finishFrameStats adds up of the quality metrics (encoder.cpp:2999-3043), IEEE doubles bit for bit in the words, in hand-out order:
  * out[13..16] the sums of the pictures' PSNR Y / U / V and of their SSIM over all pictures, out[17..20] over the I, out[21..24] the P, out[25..28] the B pictures
  * (zero unless bEnablePsnr / bEnableSsim), out[29] the largest luma sample of any source picture (an integer) and out[30] the sum of the pictures' average luma levels
- * (zero unless maxCLL or maxFALL is set).  A caller with n < 31 sees none of them. */
+ * (zero unless maxCLL or maxFALL is set).  A caller with n < 31 sees none of them.
+ * With n >= 33 also how often the start rule (x265amd_launch_plan, include/x265amd.h) gave a picture its task ahead of its turn behind a running I picture: out[31]
+ * referenced pictures (P pictures and B pictures that are references), out[32] leaf b pictures.  They depend on how fast the caller hands pictures over, the stream
+ * does not. */
 int x265amd_encoder_stats(const x265amd_encoder* enc, uint64_t* out, int n);
 /* The quality record of the picture most recently handed out by x265amd_encoder_encode / _encode_device, and the values Encoder::finishFrameStats makes of it
  * (x265amd_quality_finish, include/x265amd.h).  measured: bit 0 PSNR (ssd, psnr*), bit 1 SSIM (ssimSum: the bands' float sums added to a double in band order; ssimCnt; ssim),

@@ -405,6 +405,7 @@ extern "C" int x265amd_encoder_stats(const x265amd_encoder* e, uint64_t* out, in
         out[29] = e->statMaxCll;
         memcpy(&out[30], &e->statFallSum, 8);
     }
+    if (n >= 33) { out[31] = e->statAheadRef; out[32] = e->statAheadLeaf; }
     return 0;
 }
 extern "C" int x265amd_encoder_quality(const x265amd_encoder* e, x265amd_quality* out)
@@ -780,47 +781,56 @@ static int encoder_encode_impl(x265amd_encoder* e, x265amd_nal** ppNal, uint32_t
         e->lastTask = pic->done;
         e->running++;
     };
-    /* Tasks start in coding order while fewer than frameThreads + 1 run.  Coded in parallel, a picture without references does not wait for its turn: nothing it needs
-     * comes from another picture, and an I picture takes as long as a dozen of the others -- started when the lookahead hands it over, it is coded beside the pictures
-     * in front of it instead of holding up the ones behind it.  Output stays in coding order. */
-    const int earlyPMax = 6;
-    /* (measured, profiles/r05_early_b_sweep.txt: 2160p clips 15-22 % shorter with 12, 8-bit, Main 10 and --preset slow alike; the 1080p clips unchanged or -- the
-     * sixty-frame clip with its two scene cuts -- 15 % longer: there an I picture behind a scene cut shares the device with a dozen pictures more.  So: by size) */
-    const int earlyBMax = e->ctuH > 24 ? 12 : 0;
-    auto launch = [&]() {
-    const bool headLong = !e->inflight.empty() && (e->inflight.front()->type == TYPE_IDR || e->inflight.front()->type == TYPE_I) && e->inflight.front()->started &&
-                          e->inflight.front()->done.wait_for(std::chrono::seconds(0)) != std::future_status::ready;
-    for (auto& q : e->inflight)
-    {
-        if (q->started) continue;
-        /* the first picture in coding order always runs: it is the one collected next, whatever started ahead of its turn */
-        if (e->running <= e->frameThreads || q == e->inflight.front()) { start(q); if (e->frameThreads <= 1) q->done.wait(); continue; }
-        if (!e->frameParallel) break;
-        /* (however many I pictures run already: a limit of one helped a long 2160p clip only while P pictures started ahead of their turn all the time.  profiles/r05_sched_sweep.txt) */
-        if (q->type == TYPE_IDR || q->type == TYPE_I) start(q);
-        /* The P pictures are the chain every other picture hangs on (each follows its reference by a few CTU rows, the B pictures between two of them follow both): a P
-         * picture held back until the B pictures in front of it have been collected starts with nothing to trail and takes its full latency, so it starts when the
-         * lookahead hands it over, too (every picture it references is in front of it in coding order and therefore started). */
-        /* (round 5's end: like the B pictures below, only while a running I picture holds the head of the coding order.
-         * With P pictures ahead of their turn ALL the time a long clip stood at 52 frames/s where it reaches 100 without: the pictures far ahead held the places
-         * and the queues that the pictures collected next were waiting for; profiles/r05_sched_sweep.txt) */
-        else if (headLong && q->type == TYPE_P && e->running <= e->frameThreads + earlyPMax) start(q);
-        /* The B pictures, too (round 5), while an I picture that still runs holds the head of the coding order: `running` counts every picture that trails it and is not
-         * collected yet (collection is in coding order), and the B pictures of the mini-GOPs whose P pictures ran already waited for the I picture's END although their
-         * references were rows ahead of them -- at 2160p a third of a twenty-frame clip, at --preset slow more.  How many pictures run side by side changes nothing in
-         * what they code (the vertical reach of the vectors follows from the parameter frameNumThreads, not from this count): up to earlyBMax more than the
-         * parameter (0: in turn).  Only then, and only for large pictures (see earlyBMax above). */
-        else if (earlyBMax > 0 && headLong && e->running <= e->frameThreads + earlyBMax) start(q);
-    }
+    /* Which pictures get a task now is x265amd_launch_plan's decision (host/launch_plan.cpp, where the rules and their reasons stand): in coding order while fewer than
+     * frameThreads + 1 run; coded in parallel, an I picture when the lookahead hands it over (nothing it needs comes from another picture, and it takes as long as a
+     * dozen of the others); and while a running I picture holds the head of the coding order, the pictures of the reference chain -- P pictures AND the referenced B
+     * pictures between them: with the B pyramid and three references a P picture reads the referenced B picture of the mini-GOP before it -- ahead of their turn, then
+     * the leaf b pictures by picture size.  Never a picture whose reference has no task yet: it would park at its first CTU on a picture that starts when the I picture
+     * has ended.  (A picture another object codes counts once its task exists: the task waits for the imported rows.)  How many pictures run side by side changes
+     * nothing in what they code.  Output stays in coding order. */
+    auto launch = [&]() -> int {
+        const int n = (int)e->inflight.size();
+        if (!n) return 0;
+        std::vector<x265amd_launch_pic> plan((size_t)n);
+        std::vector<int32_t> order((size_t)n), how((size_t)n);
+        for (int i = 0; i < n; i++)
+        {
+            const Pic& q = *e->inflight[i];
+            x265amd_launch_pic& r = plan[i];
+            memset(&r, 0, sizeof(r));
+            r.type = q.type; r.referenced = q.type != TYPE_B; r.started = q.started;
+            r.finished = q.started && q.done.wait_for(std::chrono::seconds(0)) == std::future_status::ready;
+            /* its distinct reference pictures by their place in the list: coding order is consecutive, and what is not in the list any more has been collected */
+            const uint64_t first = e->inflight.front()->codingOrder;
+            for (int l = 0; l < 2; l++)
+                for (const PicP& ref : q.lists[l])
+                {
+                    const int at = ref->codingOrder >= first && ref->codingOrder < q.codingOrder && ref->codingOrder - first < (uint64_t)n &&
+                                   e->inflight[ref->codingOrder - first] == ref ? (int)(ref->codingOrder - first) : -1;
+                    bool seen = at < 0;
+                    for (int k = 0; k < r.num_refs && !seen; k++) seen = r.refs[k] == at;
+                    if (!seen && r.num_refs < X265AMD_LAUNCH_MAX_REFS) r.refs[r.num_refs++] = at;
+                }
+        }
+        int count = 0;
+        if (x265amd_launch_plan(plan.data(), n, e->running, e->frameThreads, e->ctuH, e->frameParallel, order.data(), how.data(), &count) != X265AMD_OK)
+            return xa_fail(X265AMD_EINVAL, "encoder_encode: the start rule refused the pictures in flight"), -1;
+        for (int k = 0; k < count; k++)
+        {
+            const PicP& q = e->inflight[order[k]];
+            start(q);
+            e->statAheadRef += how[k] == X265AMD_LAUNCH_AHEAD_REF; e->statAheadLeaf += how[k] == X265AMD_LAUNCH_AHEAD_LEAF;
+            if (e->frameThreads <= 1) q->done.wait();
+        }
+        return 0;
     };
-    launch();
+    if (launch()) return -1;
     /* flushing: the next mini-GOP is decided while the picture the caller will get next is still being coded */
     while (flushing && !e->input.empty())
     {
         if (!e->inflight.empty() && e->inflight.front()->started && e->inflight.front()->done.wait_for(std::chrono::seconds(0)) == std::future_status::ready) break;
         const size_t before = e->input.size();
-        if (decide() != X265AMD_OK || admit()) return -1;
-        launch();
+        if (decide() != X265AMD_OK || admit() || launch()) return -1;
         if (e->input.size() >= before) break;
     }
     if (e->inflight.empty()) return 0;

@@ -197,6 +197,7 @@ struct x265amd_encoder
     std::map<uint64_t, PicP> byCoding;                  /* the pictures in flight (and the last few collected) by their place in coding order (row export / import) */
     uint64_t collectedCoding = 0;                       /* pictures collected so far (under byCodingMu) */
     uint64_t statPictures[3] = { 0, 0, 0 }, statReferences = 0;     /* x265amd_encoder_stats: pictures prepared as I / P / B, the sum of their distinct reference pictures */
+    uint64_t statAheadRef = 0, statAheadLeaf = 0;        /* x265amd_encoder_stats: tasks started ahead of their turn behind a running I picture (x265amd_launch_plan): referenced pictures, leaf b pictures */
     uint64_t statEmitted[3] = { 0, 0, 0 }, statBits[3] = { 0, 0, 0 }; double statQpSum[3] = { 0, 0, 0 };       /* ... and of the pictures handed out: count, NAL bits, the sum of their average QPs, by I / P / B */
     /* quality metrics (param.bEnablePsnr / bEnableSsim; light levels with maxCLL || maxFALL): EncStats' sums of Encoder::finishFrameStats (encoder.cpp:2999-3043) over all
      * pictures handed out [0] and by I / P / B [1..3], the record of the last picture handed out, the device record of the light level pass (the encoder's: uploads are serial) */
